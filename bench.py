@@ -4,6 +4,8 @@ individuals on the 400-event medium01-size instance, per GPU (weak scaling:
 one independent population shard per rank, no data-path collective).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config med|lg|syn|sm]
+    python bench.py --full ...                  (plus counters, CPU baseline, oracle checks)
+    python bench.py --dump-outputs DIR ...      (the last step's outputs as DIR/<name>.npy)
     python bench.py --gpus N --config syn --global-pop 262144      (strong scaling)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
@@ -21,13 +23,26 @@ the timing barrier and the MAX all-reduce run through RCCL on a one-GPU box
 (tests/test_gpu_bench.py); the numbers are the same workload.
 
 A step is one tt_eval over the rank's whole population. Rank 0 prints one JSON
-line (BASELINE.json metric) with the dominant kernel's roofline and, at N=1, a
-CPU baseline: the reference's own computeFeasibility/Hcv/Scv (oracle/_ref,
+line (BASELINE.json metric) with the dominant kernel's roofline from the timed
+steps' own kernel time. A plain run does no more than that: set up, warm up,
+time --steps steps, write the outputs if --dump-outputs is given, print.
+
+`--full` adds everything that takes runs or work of its own. At N=1 a CPU
+baseline: the reference's own computeFeasibility/Hcv/Scv (oracle/_ref,
 OpenMP over individuals on every core this job may use) timed on a bounded
 sample of the same population. At N=1 the roofline's `traffic` and the LDS /
-VALU / SALU busy fractions are measured live: before this process touches the
+VALU / SALU busy fractions, measured live: before this process touches the
 GPU, three short child runs of the same workload under `rocprofv3 --pmc`
-(tools/pmc_live.py) read FETCH_SIZE, WRITE_SIZE and the SQ counters.
+(tools/pmc_live.py) read FETCH_SIZE, WRITE_SIZE and the SQ counters. On the
+wide path the lane phase's own timing. With a process group (N > 1 or
+TTGA_BENCH_FORCE_DIST) every rank's oracle check of its shard (`ranks`).
+--no-pmc / --no-cpu drop the first two again.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed tt_eval
+returned for this rank's shard -- hcv, scv, feasible, penalty, one value per
+individual -- as float64 DIR/<name>.npy (rank r > 0: DIR/<name>.rank<r>.npy;
+above 2^20 individuals a fixed seeded sample of the rows). The population is
+seeded, so the same arguments give the same files.
 """
 from __future__ import annotations
 
@@ -71,6 +86,11 @@ def parse():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 counter passes")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: live PMC passes, CPU baseline, "
+                         "the wide path's lane phase, every rank's oracle check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (hcv, scv, feasible, penalty) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.global_pop and args.global_pop < max(1, args.gpus):
         ap.error("--global-pop must be at least --gpus")
@@ -231,6 +251,27 @@ def verify_shard(inst, slot, room, out, rows: int = 256) -> dict:
     return rec
 
 
+OUTPUT_NAMES = ("hcv", "scv", "feasible", "penalty")
+DUMP_MAX_ROWS = 1 << 20
+
+
+def dump_outputs(directory: str, rank: int, out) -> None:
+    """The timed path's outputs of its last step, as a caller of tt_eval gets
+    them: one float64 .npy per output array (exact for i32 and u8), 32 bytes
+    per individual. Above DUMP_MAX_ROWS individuals (32 MB) the files hold a
+    fixed seeded sample of the rows, in ascending row order."""
+    d = pathlib.Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    P = int(out[0].shape[0])
+    rows = None
+    if P > DUMP_MAX_ROWS:
+        rows = np.sort(np.random.default_rng(20240).choice(P, DUMP_MAX_ROWS, replace=False))
+    for name, o in zip(OUTPUT_NAMES, out):
+        a = o.cpu().numpy()
+        suffix = "" if rank == 0 else f".rank{rank}"
+        np.save(d / f"{name}{suffix}.npy", (a if rows is None else a[rows]).astype(np.float64))
+
+
 def rank_record(rank: int, dev, kernel_ms: float, wall: float, P: int, first: int, check: dict) -> dict:
     """What one rank reports to rank 0: the device it bound (index and PCI
     location, so distinct ranks can be seen to use distinct GPUs), its kernel
@@ -260,7 +301,7 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     P, first, global_pop = rank_share(args, rank, world)
     pmc = None
-    if world == 1 and not args.no_pmc and not args.pmc_child:
+    if args.full and world == 1 and not args.no_pmc and not args.pmc_child:
         # live counters of the same workload, before this process initialises the GPU
         sys.path.insert(0, str(REPO / "tools"))
         import pmc_live
@@ -352,8 +393,10 @@ def main():
 
     if args.pmc_child:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, out)
     ranks = None
-    if use_dist:
+    if use_dist and args.full:
         # every rank checks its own shard against the oracle (outside the timed region) and
         # reports its device; rank 0 puts the gathered records into the line
         rec = rank_record(rank, dev, kernel_ms, wall, P, first, verify_shard(inst, slot, room, out))
@@ -421,7 +464,7 @@ def main():
                     "lds_cycles_per_individual": raw["SQ_LDS_IDX_ACTIVE"] / P,
                     "valu_frac": pmc.get("valu_busy"), "salu_frac": pmc.get("salu_busy"),
                     "clock_ghz": clk / 1e9}
-        if variant == 13 and not args.pmc_child:
+        if args.full and variant == 13:
             # the wide path's lane phase alone (eval_lanes: variant bit 6 skips eval_corr), on
             # the LDS byte-gather roofline: one ds_read_u8 per (individual, student id), 64 per
             # wave-instruction in 2 LDS cycles (32 banks) = 32 lookups per CU per shader cycle
@@ -442,7 +485,7 @@ def main():
                 "lookups_per_s": rate, "peak_lookups_per_s": 32 * ncu * clk,
                 "frac": rate / (32 * ncu * clk), "clock_ghz": clk / 1e9,
                 "peak_note": "ds_read_u8: 64 lanes in 2 LDS cycles (32 banks) per CU; clock from the live pass"}
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             n = args.cpu_sample
             if n <= 0:      # calibrate on a small slice, then size the sample to ~cpu_seconds
                 n0 = min(P, 256)

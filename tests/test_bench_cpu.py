@@ -26,6 +26,27 @@ def test_rank_share_weak_and_strong():
         assert max(p for p, _, _ in parts) - min(p for p, _, _ in parts) <= 1
 
 
+def test_dump_outputs_files_and_sample(tmp_path, monkeypatch):
+    """--dump-outputs: one float64 .npy per output, whole below the row cap, a
+    fixed sample (the same rows for every array and every call) above it."""
+    import numpy as np
+    import torch
+    out = [torch.arange(10, dtype=torch.int32) * k for k in (1, 2, 3)]
+    out.insert(2, (torch.arange(10) % 2).to(torch.uint8))
+    bench.dump_outputs(str(tmp_path / "a"), 0, out)
+    for name, o in zip(bench.OUTPUT_NAMES, out):
+        got = np.load(tmp_path / "a" / f"{name}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, o.numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_ROWS", 4)
+    bench.dump_outputs(str(tmp_path / "b"), 1, out)
+    bench.dump_outputs(str(tmp_path / "c"), 1, out)
+    hcv = np.load(tmp_path / "b" / "hcv.rank1.npy")
+    assert hcv.shape == (4,) and np.all(np.diff(hcv) > 0)
+    assert np.array_equal(np.load(tmp_path / "b" / "penalty.rank1.npy"), 3 * hcv)
+    assert np.array_equal(np.load(tmp_path / "c" / "hcv.rank1.npy"), hcv)
+    assert bench.DUMP_MAX_ROWS * 8 * len(bench.OUTPUT_NAMES) <= 64 << 20
+
+
 def test_gpus_above_visible_fails_loudly():
     """No GPU here: --gpus 2 must fail with rc 2 from the parent (no rank started)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "TTGA_BENCH_BACKEND")}

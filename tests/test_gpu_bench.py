@@ -22,7 +22,7 @@ def _line(out: str) -> dict:
 
 
 def test_bench_single_gpu_line():
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "20", "--warmup", "2", "--no-pmc",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "20", "--warmup", "2", "--no-pmc",
                         "--cpu-sample", "2048", "--cpu-seconds", "1"],
                        cwd=REPO, capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -38,6 +38,35 @@ def test_bench_single_gpu_line():
     assert cb["matches_gpu"] is True and cb["value"] > 0 and cb["cores"] >= 1
 
 
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full: the headline fields only (no CPU baseline, no live
+    counters, no rank checks), --steps timed steps, and --dump-outputs writes
+    the last step's four output arrays, equal to the oracle's evaluation of
+    the same seeded population."""
+    import numpy as np
+    import ttga
+    from oracle_lib import oracle
+    P = 1000
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--config", "sm",
+                        "--pop", str(P), "--dump-outputs", str(tmp_path)],
+                       cwd=REPO, capture_output=True, text=True, timeout=280)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _line(r.stdout)
+    assert d["metric"] == METRIC and d["unit"] == "evals/s" and d["higher_is_better"] is True and d["dtype"] == "i32"
+    assert d["steps"] == 7 and d["n_gpus"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert abs(d["value"] - P / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert "cpu_baseline" not in d and "ranks" not in d
+    assert d["roofline"]["traffic"] is None and "pipes" not in d["roofline"]
+    inst = ttga.config_instance("sm")
+    o = oracle().problem(inst)
+    s, rm, _ = o.random_init(ttga.population_seeds(12345, P))
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["feasible.npy", "hcv.npy", "penalty.npy", "scv.npy"]
+    for name, want in zip(("hcv", "scv", "feasible", "penalty"), o.eval(s, rm)):
+        got = np.load(tmp_path / f"{name}.npy")
+        assert got.dtype == np.float64 and got.shape == (P,)
+        assert np.array_equal(got, want.astype(np.float64)), name
+
+
 def _free_port() -> int:
     import socket
     with socket.socket() as s:
@@ -48,7 +77,7 @@ def _free_port() -> int:
 def test_bench_two_ranks_rehearsal():
     env = dict(os.environ, TTGA_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-                        "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2",
+                        "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--full", "--gpus", "2",
                         "--steps", "10", "--warmup", "2", "--no-pmc", "--no-cpu"],
                        cwd=REPO, capture_output=True, text=True, timeout=280, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -63,7 +92,7 @@ def test_bench_rccl_process_group_one_gpu():
     timing barrier and the MAX all-reduce of the N > 1 path run through RCCL
     on a one-GPU box; the line is the N = 1 line."""
     env = dict(os.environ, TTGA_BENCH_FORCE_DIST="1")
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "10", "--warmup", "2", "--no-pmc", "--no-cpu"],
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "10", "--warmup", "2", "--no-pmc", "--no-cpu"],
                        cwd=REPO, capture_output=True, text=True, timeout=280, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
@@ -76,7 +105,7 @@ def test_bench_self_launch_two_ranks():
     itself (gloo rehearsal on a one-GPU box) and relays rank 0's line."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["TTGA_BENCH_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "10", "--warmup", "2",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "2", "--steps", "10", "--warmup", "2",
                         "--no-pmc", "--no-cpu"], cwd=REPO, capture_output=True, text=True, timeout=280, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
@@ -101,7 +130,7 @@ def test_bench_self_launch_global_pop_strong():
     """--global-pop splits one population across the ranks (BASELINE configs[4])."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["TTGA_BENCH_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--global-pop", "65536", "--steps", "10",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "2", "--global-pop", "65536", "--steps", "10",
                         "--warmup", "2", "--no-pmc", "--no-cpu"], cwd=REPO, capture_output=True, text=True,
                        timeout=280, env=env)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -78,10 +78,10 @@ for s in $STEPS; do
     derive) run pytest_derive 400 python -u -m pytest tests/test_gpu_derive.py -m gpu -v --timeout 200 --timeout-method thread ;;
     newtests) run pytest_new 600 python -u -m pytest tests/test_gpu_derive.py tests/test_gpu_ga.py tests/test_gpu_parity.py -m gpu -x -v --timeout 300 --timeout-method thread -k "derive or derived or permutation or redo" ;;
     smoke) run smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 600 python -u bench.py ;;
-    benchsyn) run bench_syn 600 python -u bench.py --config syn --pop 262144 --steps 10 --warmup 2 ;;
+    bench) run bench 600 python -u bench.py --full ;;
+    benchsyn) run bench_syn 600 python -u bench.py --full --config syn --pop 262144 --steps 10 --warmup 2 ;;
     profsyn) run rocprof_syn 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_syn" -o run --output-format csv -- python -u bench.py --config syn --pop 262144 --no-pmc --no-cpu --steps 10 --warmup 2 ;;
-    benchlg) run bench_lg 600 python -u bench.py --config lg --steps 100 ;;
+    benchlg) run bench_lg 600 python -u bench.py --full --config lg --steps 100 ;;
     phases) run phases 300 python -u tools/eval_variants.py med 65536 8,24,40,72,136,264,520 ;;
     quality) run ga_quality 900 python -u tools/ga_quality.py --config sm --seeds 16 --gens 2001 --steps 200 --out "$OUT/ga_quality_sm.json" ;;
     ls)    run bench_ls 300 python -u tools/bench_ls.py --pop 4096 --steps 200 --cpu-sample 256 ;;
@@ -175,7 +175,7 @@ for s in $STEPS; do
     gacomps20) run ga_comps 900 python -u tools/ga_comps.py "$OUT/ga_comps.json" ;;
     gacomps20i2) run ga_comps_isl2 900 python -u tools/ga_comps.py "$OUT/ga_comps_isl2.json" --islands 2 ;;
     gatrace15) run ga8k_trace15 400 rocprofv3 --kernel-trace --stats -d "$OUT/ga_trace15" -o run --output-format csv -- python -u tools/bench_ga.py --config comp15 --pop 65536 --children 8192 --steps 1000 --warm-gens 96 --warm-feasible 0.6 --gens 20 --cpu-sample 0 ;;
-    selftest) run bench_self2 300 env TTGA_BENCH_BACKEND=gloo python -u bench.py --gpus 2 --steps 20 --warmup 2 --no-pmc --no-cpu ;;
+    selftest) run bench_self2 300 env TTGA_BENCH_BACKEND=gloo python -u bench.py --full --gpus 2 --steps 20 --warmup 2 --no-pmc --no-cpu ;;
     prof)  run rocprof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python -u bench.py --no-pmc --no-cpu --steps 100 ;;
     *) echo "unknown step $s"; exit 2 ;;
   esac
