@@ -175,7 +175,7 @@ def test_assign_rooms_golden(problems, name):
 
 def test_assign_rooms_random_vs_oracle(orc):
     # R = 16 / 17 and slots of exactly 32 / 33 events sit on the register
-    # matcher's limits (N <= 32, R <= 16, TT_MATCH_REG), crowded slots past them
+    # matcher's limits (N <= 32, R <= 16), crowded slots past them
     for seed, dims in [(21, (250, 12, 4, 150)), (22, (600, 30, 6, 300)), (23, (300, 16, 4, 150)),
                        (24, (300, 17, 4, 150))]:
         inst = ttga.generate(*dims, seed=seed)
@@ -269,7 +269,7 @@ def test_local_search_random_vs_oracle(orc):
 
 @pytest.mark.parametrize("name", ["tight", "med"])
 def test_local_search_noncanonical_rooms_vs_oracle(orc, problems, name):
-    """The phase-1 room-pair bounds (TT_LS_P1B) use a slot's rooms as a maximum
+    """The phase-1 room-pair bounds use a slot's rooms as a maximum
     matching only after checking that no augmenting path exists: localSearch
     from random slots with rooms that assignRooms would not give (random, and
     all room 0), on the tight instance (27 events without a possible room) and
@@ -466,7 +466,7 @@ def _hot_events(inst, s, r):
 def test_local_search_flagged_events_vs_oracle(orc):
     """GA-child-like starts: feasible individuals with one to three events moved
     to random slots, so only a few events have eventHcv > 0 and phase 1 visits
-    them through the eventHcv flags (TT_LS_HOT: the unflagged events skipped 64
+    them through the eventHcv flags (the unflagged events skipped 64
     scramble positions at a time, the flags refreshed after every accepted move).
     Slots, rooms and RNG states identical to the oracle's localSearch."""
     inst = ttga.generate(300, 12, 4, 150, seed=31)

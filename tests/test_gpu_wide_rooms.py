@@ -3,7 +3,7 @@ events through the local search, mutation, crossover, breed and replace,
 against the CPU oracle. Bit-exact (slots, rooms, RNG states).
 
 The local search has code that depends on R: the phase-1 room-pair bounds
-(TT_LS_P1B) and the register matcher (TT_MATCH_REG) exist only for R <= 16, so
+and the register matcher exist only for R <= 16, so
 R = 17..64 runs the plain wave matcher with u32/u64 room masks and no pair
 bounds. E > 448 widens every per-event structure past 7 64-bit words (EW64 > 7)
 and the matcher tasks past one wave of events. Reference: Solution.cpp:357-469

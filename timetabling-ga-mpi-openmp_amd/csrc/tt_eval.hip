@@ -36,13 +36,9 @@ typedef __attribute__((address_space(4))) const uint32_t ConstU32;
 typedef __attribute__((address_space(4))) const int32_t ConstI32;
 
 // ---------------------------------------------------------------- eval_tile5
-// TT_T5_ROOMBUF: slot-row DMA and room rows by buffer instructions (per-tile
-// resource, 32-bit lane offsets): no 64-bit per-lane pointer lives across the
-// tile loop (it spilled to scratch: 8 B per thread per tile, 4 MB per launch at
-// P = 65,536).
-#ifndef TT_T5_ROOMBUF
-#define TT_T5_ROOMBUF 1
-#endif
+// Slot-row DMA and room rows by buffer instructions (per-tile resource, 32-bit
+// lane offsets): no 64-bit per-lane pointer lives across the tile loop (it
+// spilled to scratch: 8 B per thread per tile, 4 MB per launch at P = 65,536).
 // NW waves per 64-individual tile; one tile per workgroup (the loop also runs a
 // persistent grid). Slot rows are staged by LDS-DMA (DB: two tile buffers, the
 // next tile of a persistent grid lands under the current one's evaluation).
@@ -218,8 +214,8 @@ __device__ __forceinline__ void keep_rec(const uint32_t (&r)[ST]) {
 // a run holds `cnt` students of N ids each (N even, the last id may be the
 // sentinel E), so a student costs its own events plus at most one sentinel.
 // mask_scv (>2 in a row + single class of one student's mask): tt_common.h
-// The same terms for a mask in the GAPPED slot layout of eval_lanes' tile
-// (TT_LANES_GAP): slot s = 9d + k sits at bit 10d + k for days 0-2 and at bit
+// The same terms for a mask in the GAPPED slot layout of eval_lanes' tile:
+// slot s = 9d + k sits at bit 10d + k for days 0-2 and at bit
 // 32 + 10(d - 3) + k for days 3-4, so every day is a 9-bit field followed by a
 // zero bit and no field straddles the 32-bit halves (the tile's sentinel
 // column keeps bit 63). Then:
@@ -251,9 +247,6 @@ __device__ __forceinline__ uint32_t gap_slots4(uint32_t x) {
     return x + g9 + g18 + g36 + 3u * g27;
 }
 __device__ __forceinline__ uint8_t gap_slot(uint32_t s) { return (uint8_t)gap_slots4(s); }
-#ifndef TT_LANES_GAP
-#define TT_LANES_GAP 1
-#endif
 template <bool GAP>
 __device__ __forceinline__ int mask_terms(uint64_t m) { return GAP ? mask_scv_gap(m) : mask_scv(m); }
 // K students of N ids whose dwords are r[0 .. K*N/2)
@@ -373,18 +366,11 @@ __device__ __forceinline__ int lane_scv_runs(const uint8_t* my, const DevProblem
 #ifndef TT_EVAL_ABLATE
 #define TT_EVAL_ABLATE 0
 #endif
-// Cell counters of eval_tile5 (TT_T5_CELLS = 1): [45][RW] dwords, RW = ceil(R/2),
+// Cell counters of eval_tile5: [45][RW] dwords, RW = ceil(R/2),
 // cell (s, ro) in dword s*RW + ro/2, half ro & 1 -- fewer address instructions
 // than the packed cell index (s*R + ro)/2.
-#ifndef TT_T5_CELLS
-#define TT_T5_CELLS 1
-#endif
 __host__ __device__ inline int t5_cnt_bytes(int R) {
-#if TT_T5_CELLS
     return kSlots * ((R + 1) / 2) * 4;
-#else
-    return ((kSlots * R + 1) / 2) * 4;
-#endif
 }
 
 struct Tile5Layout {
@@ -412,13 +398,12 @@ __host__ __device__ inline Tile5Layout tile5_layout(int E, int R, int NW, bool D
 // One wave's share of a tile's slot rows by LDS-DMA (global_load_lds_dword:
 // 64 lanes x 4 B land contiguously at a wave-uniform LDS address, so a row of
 // E/4 <= 112 dwords takes two instructions and keeps its padded stride SP).
-// Buffer-load form (TT_T5_ROOMBUF): a per-tile resource, a 32-bit lane offset
-// and a scalar row offset (the global form kept a 64-bit per-lane pointer live
-// across the tile loop, which spilled to scratch).
+// Buffer-load form: a per-tile resource, a 32-bit lane offset and a scalar row
+// offset (a global-pointer form kept a 64-bit per-lane pointer live across the
+// tile loop, which spilled to scratch).
 template <int NW>
 __device__ __forceinline__ void tile_dma(const uint8_t* src, uint8_t* dst, int np, int E, int SP, int wv, int lane) {
     const int qd = E >> 2;
-#if TT_T5_ROOMBUF
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, np * E, 0x00020000);
     for (int r = wv; r < np; r += NW) {
         if (lane < qd)
@@ -428,17 +413,6 @@ __device__ __forceinline__ void tile_dma(const uint8_t* src, uint8_t* dst, int n
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(dst + r * SP + 256),
                                                      4, 4 * lane + 256, r * E, 0, 0);
     }
-#else
-    for (int r = wv; r < np; r += NW) {
-        const uint32_t* g = (const uint32_t*)(src + (long)r * E);
-        auto* d = (__attribute__((address_space(3))) void*)(dst + r * SP);
-        if (lane < qd)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g + lane), d, 4, 0, 0);
-        if (lane + 64 < qd)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g + 64 + lane),
-                                             (__attribute__((address_space(3))) void*)(dst + r * SP + 256), 4, 0, 0);
-    }
-#endif
 }
 
 // Profiling build (-DTT_T5_STAMP, libttga_prof.so, tools/t5_stamps.py): per
@@ -458,24 +432,17 @@ __device__ __forceinline__ uint32_t mad_u16_hi(uint32_t a, uint32_t b, uint32_t 
     return d;
 }
 
-// TT_T5_PRIO: issue priority falls as a wave gets through its tile (3 in the
+// Issue priority falls as a wave gets through its tile (3 in the
 // lane phase, then 3, 3, 2, 2, 1, 1, 0, 0 over its wave-phase individuals), so
 // of a CU's two resident workgroups the one further behind wins the arbiter --
 // instead of the older one (round-4 stamps: the older finishes 31.9 us, its
 // neighbour 43.0 us, and the CU's last workgroup runs alone for 15 us). Same
 // box (profiles/r05_ab_tile5_prio.jsonl): med 74.2 -> 71.8 us, lg 96.9 -> 94.1,
 // comp01 100.0 -> 100.1; slower decays measured 72.1-73.1 us at med.
-#ifndef TT_T5_PRIO
-#define TT_T5_PRIO 1
-#endif
 // the schedule: priority in the lane phase, then per individual i of the wave's
-// (up to 8) wave-phase individuals nibble i of TT_T5_PRIO_W
-#ifndef TT_T5_PRIO_LANE
-#define TT_T5_PRIO_LANE 3
-#endif
-#ifndef TT_T5_PRIO_W
-#define TT_T5_PRIO_W 0x00112233u
-#endif
+// (up to 8) wave-phase individuals nibble i of kT5PrioW
+constexpr int kT5PrioLane = 3;
+constexpr uint32_t kT5PrioW = 0x00112233u;
 template <int EWC, int NW, int PK, bool DB = false>
 __global__ __launch_bounds__(64 * NW, 4) void eval_tile5_kernel(DevProblem pb, const uint8_t* __restrict__ slot,
                                                               const uint8_t* __restrict__ room, int P,
@@ -586,44 +553,33 @@ __global__ __launch_bounds__(64 * NW, 4) void eval_tile5_kernel(DevProblem pb, c
         // kept live across the tile loop, the product spilled to scratch)
         uint32_t lsp;
         asm volatile("v_mul_u32_u24 %0, %1, %2" : "=v"(lsp) : "v"(lane), "s"(SP));
-        if (TT_T5_PRIO) __builtin_amdgcn_s_setprio(TT_T5_PRIO_LANE);
+        __builtin_amdgcn_s_setprio(kT5PrioLane);
         const int sc = (!(ablate & 1) && r0 < r1) ? lane_scv_runs<1>(tile + lsp, pb, r0, r1) : 0;
         part[wv * 64 + lane] = sc;
 
         // ---- wave phase (wave = individual): hcv terms + last-slot term
         const int nq = (ablate & 2) ? 0 : np;
         uint32_t pfn[EWC];                                        // room row, one individual ahead
-#if TT_T5_ROOMBUF
         // room rows by buffer loads from a per-tile resource: a 32-bit lane offset
         // and a scalar row offset instead of a 64-bit per-lane pointer kept live
         // across the tile loop (it spilled to scratch: 8 B per thread per tile)
         const __amdgpu_buffer_rsrc_t rrs =
             __builtin_amdgcn_make_buffer_rsrc((void*)(room + p0 * E), 0, 64 * E, 0x00020000);
-        auto load_row = [&](const uint8_t*, int q, uint32_t* dst) {
+        auto load_row = [&](int q, uint32_t* dst) {
 #pragma unroll
             for (int r = 0; r < EWC; ++r)
                 dst[r] = (!last_partial || r < EWC - 1 || lane + 64 * r < E)
                              ? (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rrs, lane + 64 * r, q * E, 0)
                              : 0u;
         };
-#else
-        auto load_row = [&](const uint8_t* base, int q, uint32_t* dst) {
-            const uint8_t* rr = base + (p0 + q) * E;
-#pragma unroll
-            for (int r = 0; r < EWC; ++r)
-                dst[r] = (!last_partial || r < EWC - 1 || lane + 64 * r < E) ? rr[lane + 64 * r] : 0u;
-        };
-#endif
-        if (wv < nq) load_row(room, wv, pfn);
+        if (wv < nq) load_row(wv, pfn);
         for (int q = wv; q < nq; q += NW) {
-            if (TT_T5_PRIO) {
-                // s_setprio takes an immediate: one of four, by the schedule's nibble
-                const uint32_t pr = (TT_T5_PRIO_W >> (4 * min((q - wv) / NW, 7))) & 3u;
-                if (pr == 0) __builtin_amdgcn_s_setprio(0);
-                else if (pr == 1) __builtin_amdgcn_s_setprio(1);
-                else if (pr == 2) __builtin_amdgcn_s_setprio(2);
-                else __builtin_amdgcn_s_setprio(3);
-            }
+            // s_setprio takes an immediate: one of four, by the schedule's nibble
+            const uint32_t pr = (kT5PrioW >> (4 * min((q - wv) / NW, 7))) & 3u;
+            if (pr == 0) __builtin_amdgcn_s_setprio(0);
+            else if (pr == 1) __builtin_amdgcn_s_setprio(1);
+            else if (pr == 2) __builtin_amdgcn_s_setprio(2);
+            else __builtin_amdgcn_s_setprio(3);
             uint32_t rv[EWC], sv[EWC];
 #pragma unroll
             for (int r = 0; r < EWC; ++r) rv[r] = pfn[r];
@@ -631,7 +587,7 @@ __global__ __launch_bounds__(64 * NW, 4) void eval_tile5_kernel(DevProblem pb, c
 #pragma unroll
             for (int r = 0; r < EWC; ++r)
                 sv[r] = (!last_partial || r < EWC - 1 || lane + 64 * r < E) ? rs[lane + 64 * r] : 0u;
-            if (q + NW < nq) load_row(room, q + NW, pfn);             // next individual
+            if (q + NW < nq) load_row(q + NW, pfn);                   // next individual
             // an invalid gene anywhere -> sentinel outputs; decided from registers
             uint32_t smax = 0, rmax = 0;
 #pragma unroll
@@ -650,26 +606,16 @@ __global__ __launch_bounds__(64 * NW, 4) void eval_tile5_kernel(DevProblem pb, c
                         const uint32_t s = sv[r], ro = rv[r];
                         if (!(ablate & 8)) atomicOr((unsigned long long*)&B[s * EWC + r], 1ull << lane);
                         if (!(ablate & 16)) {                                   // Solution.cpp:148-150
-#if TT_T5_CELLS
                             // dword s*RW + ro/2: byte offset 2*(s*2RW + (ro & ~1))
                             uint32_t* c = (uint32_t*)((uint8_t*)cnt + ((__umul24(s, (uint32_t)(2 * RW)) + (ro & ~1u)) << 1));
                             const uint32_t sh = ro << 4;                        // shifts and bfe use bits 4:0
                             // (v_bfe_u32 reads offset bits 4:0, as the shift does)
                             h += (int)__builtin_amdgcn_ubfe(atomicAdd(c, 1u << (sh & 31u)), sh, 16);
-#else
-                            const uint32_t cell = s * (uint32_t)R + ro;
-                            const uint32_t sh = (cell & 1u) << 4;
-                            h += (int)((atomicAdd(&cnt[cell >> 1], 1u << sh) >> sh) & 0xFFFFu);
-#endif
                         }
                         const bool last_slot = (kLastSlotMask >> s) & 1ull;
                         if constexpr (PK == 1) {
                             h += (int)__builtin_amdgcn_ubfe(inv_ps[r], ro, 1);               // :155-156
-#if TT_T5_CELLS
                             last = (int)mad_u16_hi((uint32_t)(kLastSlotMask >> s) & 1u, inv_ps[r], (uint32_t)last);   // :93-96
-#else
-                            last += last_slot ? (int)(inv_ps[r] >> 16) : 0;             // :93-96 (unused: PK 1 with TT_T5_CELLS)
-#endif
                         } else {
                             h += (int)(((inv_poss[r] >> ro) & 1u) ^ 1u);
                             last += last_slot ? inv_sn[r] : 0;
@@ -763,11 +709,7 @@ __global__ __launch_bounds__(64 * NWL) void eval_lanes_kernel(DevProblem pb, con
                 const int r = (int)(((uint64_t)(uint32_t)w * qinv) >> 32), c = w - r * qpr;
                 const uint4 v = s16[w];
                 uint32_t* d = (uint32_t*)(tile + r * SP + 16 * c);
-                if (TT_LANES_GAP) {
-                    d[0] = gap_slots4(v.x); d[1] = gap_slots4(v.y); d[2] = gap_slots4(v.z); d[3] = gap_slots4(v.w);
-                } else {
-                    d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-                }
+                d[0] = gap_slots4(v.x); d[1] = gap_slots4(v.y); d[2] = gap_slots4(v.z); d[3] = gap_slots4(v.w);
             }
         } else {
 #pragma unroll 1
@@ -775,12 +717,12 @@ __global__ __launch_bounds__(64 * NWL) void eval_lanes_kernel(DevProblem pb, con
 #pragma unroll 1
                 for (int c = lane; c < E; c += 64) {
                     const uint8_t v = src[(long)r * E + c];
-                    tile[r * SP + c] = TT_LANES_GAP ? gap_slot(v) : v;
+                    tile[r * SP + c] = gap_slot(v);
                 }
         }
         if (threadIdx.x < 64) tile[threadIdx.x * SP + E] = 63;
         __syncthreads();
-        const int sc = r0 < r1 ? lane_scv_runs<2, TT_LANES_GAP != 0>(tile + lane * SP, pb, r0, r1) : 0;
+        const int sc = r0 < r1 ? lane_scv_runs<2, true>(tile + lane * SP, pb, r0, r1) : 0;
         part[wv * 64 + lane] = sc;
         __syncthreads();
         if (wv == 0 && lane < np) {
@@ -889,56 +831,6 @@ __device__ __forceinline__ void corr_chunk(const DevProblem& pb, int c, int lane
         }(std::make_integer_sequence<int, 4>{});
 #pragma unroll
         for (int j = 0; j < 4; ++j) x[j] = y[j];
-    }
-}
-
-// corr_chunk, software-pipelined (TT_CORR_SP): the B words of word w+1 for all
-// NB individuals are issued (volatile LDS loads: single ds_read_b64, never
-// paired into ds_read2_b64, in program order) before word w's popcounts, so
-// the compiler's lgkmcnt waits leave the next word's gathers in flight; the
-// correlation words stream from HBM/L2 four words ahead. Same-box A/B at syn
-// (profiles/r03_s2_ab.json): 5.46 ms against 5.28 for corr_chunk; off.
-#ifndef TT_CORR_SP
-#define TT_CORR_SP 0
-#endif
-template <int NB>
-__device__ __forceinline__ void corr_chunk_sp(const DevProblem& pb, int c, int lane, const uint32_t (&r)[NB],
-                                              int (&h)[NB]) {
-    typedef __attribute__((address_space(3))) volatile const uint64_t LdsWord;
-    const int E = pb.E, EW = pb.EW64, e = 64 * c + lane;
-    const bool ev = e < E;
-    const uint64_t* src = pb.cupT + (ev ? e : 0);
-    LdsWord* bp[NB];
-#pragma unroll
-    for (int q = 0; q < NB; ++q) bp[q] = (LdsWord*)(size_t)r[q];
-    uint64_t x0 = (ev && c < EW) ? src[(size_t)c * E] : 0ull;
-    uint64_t x1 = (ev && c + 1 < EW) ? src[(size_t)(c + 1) * E] : 0ull;
-    uint64_t x2 = (ev && c + 2 < EW) ? src[(size_t)(c + 2) * E] : 0ull;
-    uint64_t x3 = (ev && c + 3 < EW) ? src[(size_t)(c + 3) * E] : 0ull;
-    // ping-pong buffers a/b (no register rotation: a copy of an in-flight load
-    // would make the compiler wait for it at the copy)
-    uint64_t a[NB], b[NB];
-#pragma unroll
-    for (int q = 0; q < NB; ++q) a[q] = bp[q][c];
-    for (int w = c; w < EW; w += 2) {                              // wave-uniform
-        if (w + 1 < EW) {
-#pragma unroll
-            for (int q = 0; q < NB; ++q) b[q] = bp[q][w + 1];
-        }
-        asm volatile("" ::: "memory");                             // keep the gathers ahead of the popcounts
-        const uint64_t x4 = (ev && w + 4 < EW) ? src[(size_t)(w + 4) * E] : 0ull;
-#pragma unroll
-        for (int q = 0; q < NB; ++q) h[q] = popc_acc(x0 & a[q], h[q]);
-        if (w + 1 >= EW) break;
-        if (w + 2 < EW) {
-#pragma unroll
-            for (int q = 0; q < NB; ++q) a[q] = bp[q][w + 2];
-        }
-        asm volatile("" ::: "memory");
-        const uint64_t x5 = (ev && w + 5 < EW) ? src[(size_t)(w + 5) * E] : 0ull;
-#pragma unroll
-        for (int q = 0; q < NB; ++q) h[q] = popc_acc(x1 & b[q], h[q]);
-        x0 = x2; x1 = x3; x2 = x4; x3 = x5;
     }
 }
 
@@ -1055,11 +947,7 @@ __global__ __launch_bounds__(1024) void eval_corr_kernel(DevProblem pb, const ui
                         const uint32_t sq = (q < nq && e < E) ? (uint32_t)lds[(size_t)q * WSI + L.off_sl + e] : 0u;
                         r[q] = lds0 + (q < nq ? q : 0) * WSI + sq * BSTB;
                     }
-#if TT_CORR_SP
-                    corr_chunk_sp<NB>(pb, c, lane, r, hq);
-#else
                     corr_chunk<NB>(pb, c, lane, r, hq);
-#endif
                 }
 #pragma unroll
                 for (int q = 0; q < NB; ++q) {
@@ -1339,11 +1227,11 @@ extern "C" int tt_eval_variant(const tt_problem* p, const uint8_t* slot, const u
             // workgroups loop over their tiles with the next one staged by LDS-DMA under
             // the current one. Until round 4 it lost to one tile per workgroup (med -3 %,
             // lg -4 %, P = 262,144 -8 %: the co-resident workgroups ran in lockstep, their
-            // stagings together); with the progress-ordered issue priority (TT_T5_PRIO) it
+            // stagings together); with the progress-ordered issue priority it
             // wins (profiles/r05_ab_tile5_grid.jsonl: med 71.8 -> 69.7 us, lg 94.3 -> 92.5).
             // Without the second buffer there is nothing to overlap: one tile per workgroup.
             // ablate 64 forces the persistent grid, 128 the one-tile grid (comparisons).
-            const bool persist = (ablate & 64) || (TT_T5_PRIO && two && !(ablate & 128));
+            const bool persist = (ablate & 64) || (two && !(ablate & 128));
             const int grid = persist ? std::min(tiles, std::max(1, per_cu) * p->num_cus) : tiles;
             hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), bytes, st, p->dev, slot, room, P, hcv, scv,
                                feasible, penalty, ablate);

@@ -171,7 +171,7 @@ __global__ void bitonic_step_kernel(uint64_t* __restrict__ keys, int NP, int k, 
     }
 }
 
-// ---- merge form of the sort (TT_GA_MERGE): the survivors (positions < k = N-C)
+// ---- merge form of the sort: the survivors (positions < k = N-C)
 // of a population that a previous tt_ga_replace left sorted are already in key
 // order, so the sorted merged population is the merge of them with the C
 // children's keys sorted on their own (one workgroup in LDS for C <= kSortTile).
@@ -179,9 +179,6 @@ __global__ void bitonic_step_kernel(uint64_t* __restrict__ keys, int NP, int k, 
 // order is checked on the device; when it does not hold (a migrant written into
 // pop[N-2] survives when C = 1) a one-workgroup full sort runs instead. C = 0
 // (the initial sort) takes the tiled sort directly.
-#ifndef TT_GA_MERGE
-#define TT_GA_MERGE 1
-#endif
 
 // kPrepBlocks workgroups: flag[g] = 1 when workgroup g's share of the survivors
 // is in key order (all of them together: the survivors are); ckeys = the
@@ -246,13 +243,10 @@ __global__ __launch_bounds__(1024) void replace_fallback_sort_kernel(const int32
 }
 
 // ascending sort of tiles of T u64 keys (T a power of two, 2*KPT <= T <= kSortTile),
-// one workgroup of T/KPT threads per tile (tile blockIdx.x), the keys in registers
-// (TT_SORT_REG): thread t holds keys KPT*t..KPT*t+KPT-1; bitonic steps with j < KPT
+// one workgroup of T/KPT threads per tile (tile blockIdx.x), the keys in registers:
+// thread t holds keys KPT*t..KPT*t+KPT-1; bitonic steps with j < KPT
 // run inside a thread, KPT <= j < 64*KPT between lanes of a wave (shuffles), larger
 // j between waves through LDS (double-buffered: one barrier per step).
-#ifndef TT_SORT_REG
-#define TT_SORT_REG 1
-#endif
 template <int KPT>
 __global__ __launch_bounds__(1024) void sort_reg_kernel(uint64_t* __restrict__ keys, int T) {
     __shared__ uint64_t buf[KPT == 8 ? 2 : 1][KPT == 8 ? kSortTile : 1];
@@ -318,7 +312,7 @@ __global__ __launch_bounds__(1024) void sort_reg_kernel(uint64_t* __restrict__ k
     }
 }
 
-// ---- tiled form of the sort (TT_SORT_RANK) for kRankTile*2 <= NP <= kSortTile:
+// ---- tiled form of the sort for kRankTile*2 <= NP <= kSortTile:
 // NP/kRankTile tiles sorted by one wave each (sort_reg_kernel<4>), then every key's
 // rank in the whole array counted directly from the sorted tiles -- key x at
 // position p of tile a has rank p + sum over tiles b < a of #{y <= x} + sum over
@@ -326,9 +320,6 @@ __global__ __launch_bounds__(1024) void sort_reg_kernel(uint64_t* __restrict__ k
 // one lane per (key, tile), a binary search each, summed over the key's lanes.
 // Two launches spread over NP/kRankTile and NP*NT/256 workgroups instead of one
 // workgroup doing all 91 bitonic steps (64 us at 8,192 keys on one CU).
-#ifndef TT_SORT_RANK
-#define TT_SORT_RANK 1
-#endif
 constexpr int kRankTile = 256;
 
 // rank of keys[i] among keys[0..NP) (tiles of kRankTile sorted); every thread of
@@ -471,7 +462,7 @@ using namespace ttga;
 
 // ascending bitonic sort of NP (a power of two) u64 keys on stream st
 static void sort_keys(uint64_t* keys, int NP, hipStream_t st) {
-    if (TT_SORT_REG && NP >= 8 && NP <= kSortTile) {
+    if (NP >= 8 && NP <= kSortTile) {
         hipLaunchKernelGGL(sort_reg_kernel<8>, dim3(1), dim3(std::max(64, NP / 8)), 0, st, keys, NP);
         return;
     }
@@ -519,8 +510,8 @@ extern "C" int tt_ga_breed(const tt_problem* p, const uint8_t* pop_slot, const u
     return launch_mutation_masked(p, child_slot, child_room, rng, C, child_flags, kFlagMutate, st);
 }
 
-// NP keys in [2*kRankTile, kSortTile]: sorted by tiles + ranks (TT_SORT_RANK)
-static bool use_rank_sort(int NP) { return TT_SORT_RANK && NP >= 2 * kRankTile && NP <= kSortTile; }
+// NP keys in [2*kRankTile, kSortTile]: sorted by tiles + ranks
+static bool use_rank_sort(int NP) { return NP >= 2 * kRankTile && NP <= kSortTile; }
 // the tiles of the rank sort (ranks are then counted by the caller's kernel)
 static void sort_rank_tiles(uint64_t* keys, int NP, hipStream_t st) {
     hipLaunchKernelGGL(sort_reg_kernel<4>, dim3(NP / kRankTile), dim3(kRankTile / 4), 0, st, keys, kRankTile);
@@ -571,7 +562,7 @@ extern "C" int tt_ga_replace(const tt_problem* p, uint8_t* pop_slot, uint8_t* po
     // ga.cpp:433-434): the multi-workgroup sort, not the merge path's
     // one-workgroup fallback (which a generation meets only when a migrant
     // survives out of order, C = 1)
-    if (TT_GA_MERGE && C > 0 && C <= kSortTile) {
+    if (C > 0 && C <= kSortTile) {
         uint64_t* mkeys = (uint64_t*)(w + work_merge_offset(N, E));
         uint64_t* ckeys = (uint64_t*)((uint8_t*)mkeys + align256(8 * (size_t)N));
         int32_t* flag = (int32_t*)(ckeys + kSortTile);

@@ -51,32 +51,15 @@ __device__ unsigned long long g_ls_wave[4 * kLsWaveRec];
 #define LSP_CNT(St, i)
 #endif
 
-// TT_LS_SLP (default 0): slp[p] = slot of the event at scramble position p and
-// pos[e] = position of event e, kept with every accepted move, so a trial
-// window reads a partner's event and its slot in one LDS round trip instead
-// of two dependent ones. Same-box A/B (profiles/r03_s2_ab.json): +6 % on the
-// comp01 local search (phase 1 and 2), -2 % on med phase 2; off.
-#ifndef TT_LS_SLP
-#define TT_LS_SLP 0
-#endif
-
 struct LsLayout {
-    size_t sl, rr, nrr, evl, B, NB, rp, hist, misc, task, slp, pos, ps, sm, sinf;
+    size_t sl, rr, nrr, evl, B, NB, rp, hist, misc, task, sm, sinf;
     size_t task_bytes;
     size_t scratch;      // the task region: kLsTasks tasks, or the summaries' owner table if larger
     int NT;              // events per matcher task (min(E, 256))
     size_t bytes;
 };
 
-// TT_LS_POSS16: every event's possibleRooms mask copied into LDS as u16 when
-// R <= 16 (0.8 KB per wave at E = 400), so a matcher task's masks and the
-// phase-2 augmenting-path test read LDS instead of waiting on L2. Same-box A/B
-// (profiles/r03_s11_ab.json): comp01 phase 1 -3 %, med phase 2 +5 % (one fewer
-// wave per CU); off
-#ifndef TT_LS_POSS16
-#define TT_LS_POSS16 0
-#endif
-// TT_LS_SMASK: in phase 2 the state is feasible, so no student has two events
+// Phase-2 student masks: in phase 2 the state is feasible, so no student has two events
 // in one slot and a student's 45-bit attendance mask changes by clearing the old
 // and setting the new slot of a moved event. The masks of all students are kept
 // in LDS for phase 2 (S <= 512), and eventScv / singleClassesScv read a student's
@@ -86,19 +69,9 @@ struct LsLayout {
 // med phase-2 LS(1000) -9 % (16 waves per CU fit either way), comp01 and lg +12..18 %
 // (a second round of waves); at pop 65,536 (profiles/r03_s14_ab.json) forced masks
 // gave med -2 %, comp01 +18 %, lg +33 %.
-#ifndef TT_LS_SMASK
-#define TT_LS_SMASK 1
-#endif
 constexpr size_t kSmaskMaxBytes = 4096;
-// phase-2 share of an earlier call's steps above which the masks are worth resident waves
-#ifndef TT_LS_MASK_SHARE
-#define TT_LS_MASK_SHARE 0.5
-#endif
-// TT_LS_P1B: phase-1 room-pair lower bounds (below, SlotInfo) from a summary
+// Phase-1 room-pair lower bounds (below, SlotInfo) from a summary
 // of a maximum matching of every slot (45 x 20 B per wave + 128 B scratch).
-#ifndef TT_LS_P1B
-#define TT_LS_P1B 1
-#endif
 // (R <= 16: the room sets fit 16 bits, a summary 8 bytes)
 struct SlotInfo {
     uint16_t used;       // rooms matched in a maximum matching of the slot
@@ -111,13 +84,9 @@ constexpr int kP1bMaxRooms = 16;
 constexpr size_t kSinfBytes = sizeof(SlotInfo) * (kSlots + 3);
 // A matcher task: ev [NT] u16 and hist [R] u16 (the wave matcher's), then, only
 // where a slot of more than 64 events can reach the lane-serial matcher (NT > 64),
-// its pl [NT] u64, mr [NT], rm [R] and dr [R]. TT_LS_TASK_COMPACT = 0 allocates
-// the serial matcher's arrays in every launch (the round-4 layout's size: 11 NT +
-// 4 R bytes per task, against 2 NT + 2 R; at E >= 64 the first launch's three
-// tasks take 2.3 KB of a wave's LDS instead of 0.5 KB).
-#ifndef TT_LS_TASK_COMPACT
-#define TT_LS_TASK_COMPACT 1
-#endif
+// its pl [NT] u64, mr [NT], rm [R] and dr [R] (11 NT + 4 R bytes per task, against
+// 2 NT + 2 R; at E >= 64 the first launch's three tasks take 0.5 KB of a wave's
+// LDS instead of 2.3 KB).
 __host__ __device__ inline size_t task_off_pl(int NT, int R) { return (2 * (size_t)NT + 2 * (size_t)R + 7) & ~(size_t)7; }
 // cap: events per matcher task (kLsCapSmall for the first launch, kMaxSlotEvents for the redo launch)
 // S: students with phase-2 masks (0: none)
@@ -129,36 +98,21 @@ __host__ __device__ inline LsLayout ls_layout(int E, int R, int EW, int cap, int
     L.rr = b; b += E;
     L.nrr = b; b += E;
     al(2); L.evl = b; b += 2 * (size_t)E;
-#if TT_LS_SLP
-    L.pos = b; b += 2 * (size_t)E;
-    L.slp = b; b += (size_t)E;
-#else
-    L.pos = L.slp = 0;
-#endif
-#if TT_LS_POSS16
-    L.ps = b; if (R <= 16) b += 2 * (size_t)E;        // possibleRooms as u16 (R <= 16)
-#else
-    L.ps = 0;
-#endif
     al(8);
-#if TT_LS_SMASK
     L.sm = b; if (S > 0 && 8 * (size_t)S <= kSmaskMaxBytes) b += 8 * (size_t)S;   // phase-2 student masks (S = smS)
-#else
-    L.sm = 0;
-#endif
     L.B = b; b += 8 * (size_t)kSlots * EW;
     L.NB = b; b += 8 * (size_t)kLsTasks * EW;
     L.rp = b; b += 4 * (size_t)kSlots;
     L.hist = b; b += 2 * (size_t)kSlots * R;
     // phase-1 slot summaries: aliased with the phase-2 student masks when those exist
     L.sinf = 0;
-    if (TT_LS_P1B && R <= kP1bMaxRooms) {
+    if (R <= kP1bMaxRooms) {
         if (L.sm && S > 0 && 8 * (size_t)S <= kSmaskMaxBytes && 8 * (size_t)S >= kSinfBytes) L.sinf = L.sm;
         else { al(8); L.sinf = b; b += kSinfBytes; }
     }
     al(4); L.misc = b; b += 4 * 32;
     L.NT = E < cap ? E : cap;
-    L.task_bytes = (task_off_pl(L.NT, R) + (L.NT > 64 || !TT_LS_TASK_COMPACT ? 9 * (size_t)L.NT + 2 * (size_t)R : 0) + 15) &
+    L.task_bytes = (task_off_pl(L.NT, R) + (L.NT > 64 ? 9 * (size_t)L.NT + 2 * (size_t)R : 0) + 15) &
                    ~(size_t)15;
     al(16); L.task = b;
     L.scratch = kLsTasks * L.task_bytes;
@@ -186,11 +140,9 @@ struct LsState {
     int E, R, EW, lane;
     uint8_t *sl, *rr, *nrr;
     uint16_t* evl;
-    uint16_t* pos;       // [E] position of each event in evl (TT_LS_SLP)
-    uint8_t* slp;        // [E] slot of the event at each position (TT_LS_SLP)
     uint64_t *B, *NB;
-    const uint16_t* ps;  // [E] possibleRooms in LDS (R <= 16), else null (TT_LS_POSS16)
-    uint64_t* sm;        // [S] phase-2 attendance masks (TT_LS_SMASK), null outside phase 2
+    const uint16_t* ps;  // [E] possibleRooms as u16 in LDS; no layout allocates them: always null
+    uint64_t* sm;        // [S] phase-2 attendance masks, null outside phase 2
     int32_t* rp;
     uint16_t* hist;
     int32_t* misc;       // [0..2] neighbour room pairs per task, [3] redo flag, [4..6] events per task
@@ -207,7 +159,7 @@ struct LsState {
     // phase 2: the state stays feasible, so every slot's rooms are distinct and
     // hist[] is reused as the owner table oe[slot * R + room] (event, 0xFFFF free)
     int phase2;
-    // phase-1 pair bounds (TT_LS_P1B): per-slot matching summaries; null sinf: off.
+    // phase-1 pair bounds: per-slot matching summaries; null sinf: off.
     // one base pointer: sinf[45] of the slots, then tsi[3] of the matcher tasks
     SlotInfo* sinf;
     int tvalid;          // bit k: tsi[k] describes the current neighbour's task k
@@ -259,17 +211,13 @@ __device__ __forceinline__ int corr_in_set(LsState& S, int e, const uint64_t* se
     return c - self;
 }
 
-// TT_LS_ROWB: a lane's own correlation row (corr64[e], EW words in L2) against an
+// A lane's own correlation row (corr64[e], EW words in L2) against an
 // LDS word set, loaded 8 words at a time with all 8 loads in flight before the
 // first is used -- the plain word loop waited out one L2 round trip per word
 // (EW of them per row; 49 per whole-population pass at E = 400).
-#ifndef TT_LS_ROWB
-#define TT_LS_ROWB 1
-#endif
 // sum over w < EW of popcount(row[w] & set[w]) minus the row's own bit e
 __device__ __forceinline__ int row_pop_in(const uint64_t* __restrict__ row, const uint64_t* set, int EW, int e) {
     int c = 0;
-#if TT_LS_ROWB
     for (int w0 = 0; w0 < EW; w0 += 8) {
         uint64_t x[8];
 #pragma unroll
@@ -280,10 +228,6 @@ __device__ __forceinline__ int row_pop_in(const uint64_t* __restrict__ row, cons
             if (w0 + k == (e >> 6)) c -= (int)((x[k] >> (e & 63)) & 1ull);
         }
     }
-#else
-    for (int w = 0; w < EW; ++w) c += __popcll(row[w] & set[w]);
-    c -= (int)((row[e >> 6] >> (e & 63)) & 1ull);
-#endif
     return c;
 }
 
@@ -388,21 +332,14 @@ __device__ __forceinline__ void scv_terms(LsState& S, int e, bool nb, int& es, i
     LSP_ADD(S, kPfScv, t0);
 }
 
-// TT_LS_DISC_ALL: the room stage's discovering-room ballot over all room lanes,
-// masked by the uniform M afterwards (no per-lane M test).
-#ifndef TT_LS_DISC_ALL
-#define TT_LS_DISC_ALL 1
-#endif
-// TT_LS_WLT: the matcher's room transpose by v_writelane instead of a
-// compare-and-select per room.
-#ifndef TT_LS_WLT
-#define TT_LS_WLT 1
-#endif
+// The wave matcher: the room stage's discovering-room ballot runs over all room
+// lanes, masked by the uniform M afterwards (no per-lane M test); the room
+// transpose is by v_writelane instead of a compare-and-select per room.
 // (writelane64 is in tt_match.h; nothing else in the local-search kernel uses
 // M0 -- no LDS-DMA, no movrel.)
 
 // Wave matcher for one touched slot of N <= 64 events, the same search as
-// match_slot<1> (tt_match.h, Solution.cpp:772-891), with its state in
+// match_slot (tt_match.h, Solution.cpp:772-891), with its state in
 // registers: lane i holds event i's possible-room mask (pl) and matched room
 // (mr); lane j holds room j's matched event (rm), search dad (dr) and the mask
 // of the slot's events that may use it (ev_of_room); the seen/fringe sets are
@@ -424,8 +361,7 @@ __device__ __forceinline__ void match_task_wave(LsState& S, int k, int N, int ev
     const uint32_t pl_lo = (uint32_t)pl, pl_hi = (uint32_t)(pl >> 32);
     // transpose: ev_of_room (lane j) = the events whose possible rooms include j:
     // one ballot per room, written into lane j by v_writelane; pl is zero past the
-    // N events (load_tasks)
-#if TT_LS_WLT
+    // N events (match_tasks)
     uint32_t eor_lo = 0, eor_hi = 0;
     {
         const int r1 = R < 32 ? R : 32;
@@ -433,16 +369,6 @@ __device__ __forceinline__ void match_task_wave(LsState& S, int k, int N, int ev
         for (int j = 32; j < R; ++j) writelane64(eor_lo, eor_hi, ballot((pl_hi >> (j - 32)) & 1u), j);
     }
     const uint64_t eor = ((uint64_t)eor_hi << 32) | eor_lo;
-#else
-    uint64_t eor = 0;
-    for (int j0 = 0; j0 < R; j0 += 4) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const uint64_t b = ballot((pl >> (j0 + q)) & 1ull);
-            if (lane == j0 + q) eor = b;
-        }
-    }
-#endif
     // lane j also keeps the possible rooms of its matched event (plr), so a
     // search step reads rm and plr at the same lane j: no dependent readlane
     uint32_t mr = NONE, rm = 0, dr = 0, plr_lo = 0, plr_hi = 0;
@@ -467,11 +393,7 @@ __device__ __forceinline__ void match_task_wave(LsState& S, int k, int N, int ev
             const uint64_t freef = fr & ~rmatched;
             const uint64_t M = fr & (freef ? (freef & (0ull - freef)) - 1ull : ~0ull);
             const uint64_t plr = ((uint64_t)plr_hi << 32) | plr_lo;
-#if TT_LS_DISC_ALL
             const uint64_t disc = ballot((plr & ~sr) != 0ull) & M;      // M is uniform: mask after the ballot
-#else
-            const uint64_t disc = ballot(((M >> lane) & 1ull) && (plr & ~sr) != 0ull);
-#endif
             LSP_CNT(S, kPfMatchSteps);
             if (!disc) {                                   // the walk reaches the lowest free room
                 if (freef) sink = __builtin_ctzll(freef);
@@ -561,38 +483,15 @@ __device__ __forceinline__ void match_task_wave(LsState& S, int k, int N, int ev
 }
 
 // Lane-serial matcher for a touched slot of 64 < N <= 256 events (one lane):
-// rare, so out of line (TT_LS_SERIAL_CALL) -- inlined at each of match_tasks'
-// call sites it made up much of the kernel's 166 KB of code. Returns the
-// slot's room-clash pairs; the rooms go to nrr.
-#ifndef TT_LS_TASK_LOOP
-#define TT_LS_TASK_LOOP 1
-#endif
-#ifndef TT_LS_M1WIN
-#define TT_LS_M1WIN 1
-#endif
-// visit rows one visit ahead: same-box A/B +2..+11 % (profiles/r03_s5_ab.json); off
-#ifndef TT_LS_ROWPF
-#define TT_LS_ROWPF 0
-#endif
-// With the phase-1 eventHcv flags a skip moves the visit index by several
-// positions, so a row prefetched for position i+1 would belong to the wrong
-// event: the two are exclusive.
-#if TT_LS_ROWPF && (!defined(TT_LS_HOT) || TT_LS_HOT)
-#error "TT_LS_ROWPF needs TT_LS_HOT=0 (a flag skip invalidates the prefetched row)"
-#endif
-#ifndef TT_LS_SERIAL_CALL
-#define TT_LS_SERIAL_CALL 1
-#endif
-#if TT_LS_SERIAL_CALL
+// rare, so out of line -- inlined at each of match_tasks' call sites it made up
+// much of the kernel's 166 KB of code. Returns the slot's room-clash pairs; the
+// rooms go to nrr.
 __device__ __noinline__
-#else
-__device__ __forceinline__
-#endif
 int match_task_serial(int R, int N, const uint64_t* poss, uint16_t* ev, uint64_t* pl, uint8_t* mr, uint8_t* rm,
                       uint8_t* dr, uint16_t* hist, uint8_t* nrr) {
     for (int i = 0; i < N; ++i) pl[i] = poss[ev[i]];
     for (int r = 0; r < R; ++r) hist[r] = 0;
-    match_slot<4>(R, ev, pl, N, mr, rm, dr, nrr);
+    match_slot(R, ev, pl, N, mr, rm, dr, nrr);
     int pairs = 0;
     for (int i = 0; i < N; ++i) {
         const int r = nrr[ev[i]];
@@ -634,7 +533,7 @@ __device__ __forceinline__ void build_nb(LsState& S) {
 }
 
 // Lists the events of each touched slot for the matcher (lane k lists slot k);
-// done only for trials that reach a matching.
+// done only for trials that reach a matching, once per trial (S.listed).
 __device__ __forceinline__ void list_tasks(LsState& S) {
     LSP_T(t0);
     const int EW = S.EW;
@@ -655,72 +554,27 @@ __device__ __forceinline__ void list_tasks(LsState& S) {
 }
 
 // Re-matches the touched slots in kmask (after build_nb): the wave matcher runs
-// the slots one after another (the lane-serial match_slot<4> for a slot of more
+// the slots one after another (the lane-serial match_slot for a slot of more
 // than 64 events). Returns true when the first launch must redo the individual.
-struct TaskRegs {
-    int tn[3], tev[3];
-    uint64_t tpl[3];
-};
-
-// TT_LS_TASK_LATE: a task's events and possible rooms are loaded in the task
-// loop right before its matching, instead of all three tasks' at once ahead of
-// the loop: the 12 VGPRs of the early form stay live across the inlined
-// matcher, which at the kernel's 96 VGPRs spilled them to scratch (the largest
-// group of the kernel's scratch accesses)
-#ifndef TT_LS_TASK_LATE
-#define TT_LS_TASK_LATE 1
-#endif
-// every task's events and possible rooms into registers at once (one L2 round
-// trip), issued as early as the trial allows so the latency overlaps other work
-__device__ __forceinline__ TaskRegs load_tasks(LsState& S, int kmask) {
+// A task's events and possible rooms are loaded in the task loop right before
+// its matching, not all three tasks' at once ahead of the loop: the 12 VGPRs of
+// the early form stay live across the inlined matcher, which at the kernel's 96
+// VGPRs spilled them to scratch (the largest group of the kernel's scratch
+// accesses). The tasks must be listed (list_tasks): match_tasks below sees to it.
+__device__ __forceinline__ bool match_listed_tasks(LsState& S, int kmask) {
     // task 1 kept from the previous rejected Move1 trial (set only inside a phase-1 Move1 loop)
-    if (S.c1_valid && S.nts == 2) kmask &= ~2;
-    if (!S.listed) {
-        list_tasks(S);
-        S.listed = 1;
-    }
-    TaskRegs r;
-    if (TT_LS_TASK_LATE) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { r.tn[k] = 0; r.tev[k] = 0; r.tpl[k] = 0ull; }
-        return r;
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        r.tn[k] = k < S.nts && ((kmask >> k) & 1) ? S.misc[4 + k] : 0;
-        const bool a = S.lane < r.tn[k] && r.tn[k] <= 64;
-        r.tev[k] = a ? get_task(S, k).ev[S.lane] : 0;
-        r.tpl[k] = a ? poss_of(S, r.tev[k]) : 0ull;
-    }
-    return r;
-}
-
-__device__ __forceinline__ bool match_tasks(LsState& S, int kmask, const TaskRegs& tr) {
     if (S.c1_valid && S.nts == 2) kmask &= ~2;
     if (!(kmask & ((1 << S.nts) - 1))) return false;            // nothing to match: no sync
     LSP_T(t0);
-    // TT_LS_TASK_LOOP: the task loop stays a loop (one inlined matcher per call
-    // site instead of three); the task's registers are picked by selects
-#if TT_LS_TASK_LOOP
+    // the task loop stays a loop (one inlined matcher per call site instead of three)
 #pragma unroll 1
-#else
-#pragma unroll
-#endif
     for (int k = 0; k < 3; ++k) {
         if (k >= S.nts) break;
         if (!((kmask >> k) & 1)) continue;
-        int N, tevk;
-        uint64_t tplk;
-        if (TT_LS_TASK_LATE) {
-            N = __builtin_amdgcn_readfirstlane(S.misc[4 + k]);
-            const bool a = S.lane < N && N <= 64;
-            tevk = a ? get_task(S, k).ev[S.lane] : 0;
-            tplk = a ? poss_of(S, tevk) : 0ull;
-        } else {
-            N = k == 0 ? tr.tn[0] : k == 1 ? tr.tn[1] : tr.tn[2];
-            tevk = k == 0 ? tr.tev[0] : k == 1 ? tr.tev[1] : tr.tev[2];
-            tplk = k == 0 ? tr.tpl[0] : k == 1 ? tr.tpl[1] : tr.tpl[2];
-        }
+        const int N = __builtin_amdgcn_readfirstlane(S.misc[4 + k]);
+        const bool a = S.lane < N && N <= 64;
+        const int tevk = a ? get_task(S, k).ev[S.lane] : 0;
+        const uint64_t tplk = a ? poss_of(S, tevk) : 0ull;
         if (N > S.NT) {                                             // task capacity exceeded
             if (S.lane == 0) {
                 if (S.NT < kMaxSlotEvents && S.NT < S.E) {
@@ -752,10 +606,12 @@ __device__ __forceinline__ bool match_tasks(LsState& S, int kmask, const TaskReg
     return S.misc[3] != 0;
 }
 
+// match_listed_tasks after listing the tasks, once per trial
 __device__ __forceinline__ bool match_tasks(LsState& S, int kmask) {
     if (S.c1_valid && S.nts == 2) kmask &= ~2;
-    if (!(kmask & ((1 << S.nts) - 1))) return false;            // nothing to match: no listing, no loads
-    return match_tasks(S, kmask, load_tasks(S, kmask));
+    if (!(kmask & ((1 << S.nts) - 1))) return false;            // nothing to match: no listing
+    if (!S.listed) { list_tasks(S); S.listed = 1; }
+    return match_listed_tasks(S, kmask);
 }
 
 __device__ __forceinline__ bool build_and_match(LsState& S) {
@@ -865,9 +721,6 @@ __device__ __forceinline__ void accept(LsState& S) {
         for (int q = 0; q < 3; ++q)
             if (q < S.nmv) {
                 S.sl[S.mv_e[q]] = (uint8_t)S.mv_t[q];
-#if TT_LS_SLP
-                S.slp[S.pos[S.mv_e[q]]] = (uint8_t)S.mv_t[q];
-#endif
             }
     }
     wave_sync();
@@ -1037,7 +890,7 @@ __device__ __forceinline__ bool matchable(LsState& S, int s, int out, int a) {
     return false;
 }
 
-// ---- phase-1 room-pair lower bounds (TT_LS_P1B). A phase-1 trial from an
+// ---- phase-1 room-pair lower bounds. A phase-1 trial from an
 // infeasible state mostly fails on room clashes, which the correlation bounds
 // above cannot see, so it used to run the full matcher of every touched slot
 // just to be rejected. assignRooms (Solution.cpp:772-891) computes a MAXIMUM
@@ -1301,7 +1154,7 @@ __device__ __forceinline__ int wrap_e(int x, int E) {
     return x;
 }
 
-// TT_LS_HOT (phase 1): the events with eventHcv > 0 as a bitmask over event
+// Phase-1 hot flags: the events with eventHcv > 0 as a bitmask over event
 // ids, one word per lane (lane w: events 64w..64w+63). A visit of an event
 // with eventHcv == 0 only counts towards evCount (no draw, no step:
 // Solution.cpp:509-512), so the visit loop jumps over such events 64 scramble
@@ -1312,9 +1165,6 @@ __device__ __forceinline__ int wrap_e(int x, int E) {
 // (a GA child of feasible parents); from a random solution nearly every event
 // is visited anyway and the flags' upkeep after every accepted move only costs.
 // (The flags in LDS instead of a register measured slower: 136 VGPRs spilled.)
-#ifndef TT_LS_HOT
-#define TT_LS_HOT 1
-#endif
 // The flags of events 64k + lane; with `all` every event, else
 // only those in a touched slot (S.ts, after accept) replace their flag in `hot`
 // (lane k holds word k)
@@ -1430,9 +1280,8 @@ __device__ __attribute__((always_inline)) inline void ls_one(const DevProblem& p
     S.pb = pb; S.E = E; S.R = R; S.EW = EW; S.lane = lane;
     S.sl = lds + L.sl; S.rr = lds + L.rr; S.nrr = lds + L.nrr;
     S.evl = (uint16_t*)(lds + L.evl);
-    S.pos = (uint16_t*)(lds + L.pos); S.slp = lds + L.slp;
     S.B = (uint64_t*)(lds + L.B); S.NB = (uint64_t*)(lds + L.NB);
-    S.ps = (TT_LS_POSS16 && R <= 16) ? (const uint16_t*)(lds + L.ps) : nullptr;
+    S.ps = nullptr;
     S.sm = nullptr;
     S.rp = (int32_t*)(lds + L.rp); S.hist = (uint16_t*)(lds + L.hist);
     S.misc = (int32_t*)(lds + L.misc);
@@ -1530,14 +1379,6 @@ __device__ __attribute__((always_inline)) inline void ls_one(const DevProblem& p
         }
     }
     __syncthreads();
-#if TT_LS_SLP
-    for (int q = lane; q < E; q += 64) {
-        const int e = S.evl[q];
-        S.pos[e] = (uint16_t)q;
-        S.slp[q] = S.sl[e];
-    }
-    __syncthreads();
-#endif
     LSP_ADD(S, kPfScramble, t_scr);
 
     LSP_ADD(S, kPfInit, t_kernel);
@@ -1553,21 +1394,15 @@ __device__ __attribute__((always_inline)) inline void ls_one(const DevProblem& p
     const bool fast1 = EW <= 64;                                        // row words fit the lanes
     LSP_SET(t_ph);
     if (!feasible_now(S)) {                                             // phase 1 (Solution.cpp:497-618)
-        // TT_LS_ROWPF: the visited event's correlation row loaded one visit ahead
-        // (the scrambled event list is fixed, so the next visit's event is known)
-        uint64_t nrow = (fast1 && TT_LS_ROWPF) ? load_row(S, S.evl[0]) : 0ull;
         uint64_t hot = 0;
         int nhot = 0;
-        if (TT_LS_HOT && fast1) {
+        if (fast1) {
             hot = refresh_hot(S, 0ull, true);
             nhot = wave_sum(lane < EW ? __popcll(hot) : 0);
         }
-        const bool hotm = TT_LS_HOT && fast1 && 4 * nhot <= E;
-        // many events in conflict: room-pair lower bounds before the matcher (TT_LS_P1B)
-#ifndef TT_LS_P1B_RTOFF
-#define TT_LS_P1B_RTOFF 0       // profiling: the bounds compiled in but never enabled (p1 < 2 always)
-#endif
-        if (TT_LS_P1B && R <= kP1bMaxRooms && !hotm && fast1 && !(TT_LS_P1B_RTOFF && p1 < 2.0)) {
+        const bool hotm = fast1 && 4 * nhot <= E;
+        // many events in conflict: room-pair lower bounds before the matcher
+        if (R <= kP1bMaxRooms && !hotm && fast1) {
             S.sinf = (SlotInfo*)(lds + L.sinf);
             sinf_init(S);
         }
@@ -1590,7 +1425,7 @@ __device__ __attribute__((always_inline)) inline void ls_one(const DevProblem& p
         S.sinf = nullptr;
         if (ph_steps && lane == 0) S.misc[8] = step;                   // phase-1 steps (for the statistics)
         for (int c = lane; c < kSlots * R; c += 64) S.hist[c] = 0xFFFF;
-        if (TT_LS_SMASK && smS > 0) {
+        if (smS > 0) {
             S.sm = (uint64_t*)(lds + L.sm);
             for (int st = lane; st < pb.S; st += 64) {
                 uint64_t m = 0;
@@ -1603,15 +1438,12 @@ __device__ __attribute__((always_inline)) inline void ls_one(const DevProblem& p
         wave_sync();
         const bool fast = fast1;
         evc = 0;
-        uint64_t nrow = (fast && TT_LS_ROWPF) ? load_row(S, S.evl[0]) : 0ull;
         for (int i = 0; evc < E; i = wrap_e(i + 1, E)) {
             if (step > max_steps || ++guard > guard_max) break;
             const int ei = S.evl[i];
             LSP_CNT(S, kPfVisits);
             LSP_T(t_vis);
-            uint64_t row = nrow;
-            if (fast && TT_LS_ROWPF) nrow = load_row(S, S.evl[i + 1 < E ? i + 1 : 0]);
-            else if (fast) row = load_row(S, ei);
+            const uint64_t row = fast ? load_row(S, ei) : 0ull;
             int cur, scs_i;
             scv_terms(S, ei, false, cur, scs_i);
             if (cur == 0) { evc++; LSP_ADD(S, kPfVis2, t_vis); continue; }
@@ -1679,14 +1511,7 @@ __device__ __attribute__((always_inline)) inline void ls_one(const DevProblem& p
                         // moved event in its new slot)
                         const int rem = wrap_e(i - j + E, E);
                         // (ds_bpermute reads 0 from inactive lanes: every lane takes part)
-#if TT_LS_SLP
-                        int pk = j + lane;
-                        if (pk >= E) pk -= E;
-                        if (pk >= E) pk %= E;                      // E < 64 only
-                        const int ej = S.evl[pk], tj = S.slp[pk];
-#else
                         const int ej = S.evl[wrap_e(j + lane, E)], tj = S.sl[ej];
-#endif
                         const uint64_t rw = bperm64(V.row, ej >> 6), zw = bperm64(V.z, ej >> 6);
                         const int xt = bperm(V.x, tj);
                         bool need = true;
@@ -1725,12 +1550,12 @@ __device__ __attribute__((always_inline)) inline void ls_one(const DevProblem& p
                         set_move(S, 2, ei, ej, 0);
                         build_nb(S);
                         if (!quick && corr_nb(S, ei) + corr_nb(S, ej) != 0) break;   // eah_nb > 0 whatever the rooms
-                        const TaskRegs tr = load_tasks(S, 7);
+                        if (!S.listed) { list_tasks(S); S.listed = 1; }
                         if (S.nts == 2) {
-                            if (match_tasks(S, 1, tr)) goto redo;
+                            if (match_listed_tasks(S, 1)) goto redo;
                             if (S.misc[0] != 0) { restore_task<0>(S); break; }
-                            if (match_tasks(S, 2, tr)) goto redo;
-                        } else if (match_tasks(S, 7, tr)) goto redo;
+                            if (match_listed_tasks(S, 2)) goto redo;
+                        } else if (match_listed_tasks(S, 7)) goto redo;
                         if (S.misc[task_of(S, slot_nb(S, ei))] + S.misc[task_of(S, slot_nb(S, ej))] == 0) {
                             int es_ni, scs_ni, es_nj, scs_nj, es_cj, scs_cj;
                             scv_terms(S, ei, true, es_ni, scs_ni);
@@ -1820,14 +1645,12 @@ redo:
     }
 }
 
-#ifndef TT_LS_WPE
-#define TT_LS_WPE 5
-#endif
+constexpr int kLsWpe = 5;    // amdgpu_waves_per_eu of both kernels
 // First launch: one wave per individual, in dispatch order `order` (NULL:
 // 0..P-1; entries outside 0..P-1 are skipped, tt_local_search_ordered checks
 // the permutation).
 template <int CAP>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TT_LS_WPE))) void local_search_kernel(
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLsWpe))) void local_search_kernel(
     DevProblem pb, uint8_t* __restrict__ slot, uint8_t* __restrict__ room, int64_t* __restrict__ rng, int P,
     int max_steps, double p1, double p2, double p3, int32_t* __restrict__ redo_list, int redo_cap,
     const int32_t* __restrict__ order, int smS, unsigned long long* __restrict__ ph_steps, LsEvalOut eout) {
@@ -1841,7 +1664,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TT_LS_WPE)))
 // resets the list for the stream's next call (no per-call memset). With an
 // empty list every wave returns at once (the arrival count is only needed when
 // there is a list to reset: 52 -> a few us per GA generation).
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TT_LS_WPE))) void local_search_redo_kernel(
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLsWpe))) void local_search_redo_kernel(
     DevProblem pb, uint8_t* __restrict__ slot, uint8_t* __restrict__ room, int64_t* __restrict__ rng, int max_steps,
     double p1, double p2, double p3, int32_t* __restrict__ redo_list, int redo_cap, int smS,
     unsigned long long* __restrict__ ph_steps, LsEvalOut eout) {
@@ -1918,7 +1741,7 @@ extern "C" int tt_ls_prof_read(unsigned long long* out, int reset) {
 template <typename K>
 static int ls_mask_occupancy(const tt_problem* p, int cap, K k) {
     const int S = p->dev.S;
-    if (!TT_LS_SMASK || S <= 0 || 8 * (size_t)S > kSmaskMaxBytes) return 0;
+    if (S <= 0 || 8 * (size_t)S > kSmaskMaxBytes) return 0;
     const size_t b0 = ls_layout(p->E, p->R, p->dev.EW64, cap, 0).bytes, b1 = ls_layout(p->E, p->R, p->dev.EW64, cap, S).bytes;
     int o0 = 0, o1 = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o0, k, 64, b0) != hipSuccess ||
@@ -1940,16 +1763,13 @@ static int ls_mask_occupancy(const tt_problem* p, int cap, K k) {
 // (profiles/r05_ab_ga_ls_masks.jsonl): masks at 18 instead of 20 waves per CU
 // give comp01 (mostly phase 2) +5 %, comp10 -2 % and comp15 (phase 1 only) -4 %.
 // The masks never change a result, only the launch's speed.
-constexpr double kLsMaskShare = TT_LS_MASK_SHARE;
+constexpr double kLsMaskShare = 0.5;
 template <typename K>
 static int ls_mask_students(const tt_problem* p, int cap, K k, int P, double share2 = -1.0) {
     std::atomic<int>& memo = const_cast<tt_problem*>(p)->ls_smask[cap == kMaxSlotEvents ? 0 : 1];
     int m = memo.load(std::memory_order_relaxed);
     if (m < 0) memo.store(m = ls_mask_occupancy(p, cap, k), std::memory_order_relaxed);
     if (m == 0) return 0;
-#ifdef TT_LS_SMASK_FORCE
-    return p->dev.S;                            // profiling: masks whatever the occupancy
-#endif
     const int o0 = m >> 8, o1 = m & 255;
     const long per_cu = ((long)P + p->num_cus - 1) / p->num_cus;
     return (o1 >= o0 || per_cu <= o1 || share2 >= kLsMaskShare) ? p->dev.S : 0;

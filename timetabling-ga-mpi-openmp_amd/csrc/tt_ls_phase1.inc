@@ -34,9 +34,8 @@
             const int ei = S.evl[i];
             LSP_CNT(S, kPfVisits);
             LSP_T(t_vis);
-            uint64_t row = nrow;
-            if (fast1 && TT_LS_ROWPF) nrow = load_row(S, S.evl[i + 1 < E ? i + 1 : 0]);
-            else if (fast1) row = load_row(S, ei);
+            uint64_t row = 0ull;
+            if (fast1) row = load_row(S, ei);
             // eventHcv(ei) (Solution.cpp:173-191); known > 0 from the flags
             const int ehcv = hotm ? 1
                              : fast1 ? (int)S.hist[S.sl[ei] * R + S.rr[ei]] - 1 +
@@ -56,14 +55,14 @@
             const int t_start = pm_pick(st, kSlots);
             for (int h = 0; h < kSlots;) {
                 if (step > max_steps) break;
-                if (TT_LS_M1WIN && fast1 && S.c1_valid && (uint64_t)st < kPmM) {
+                if (fast1 && S.c1_valid && (uint64_t)st < kPmM) {
                     // window: lane k screens target t_start+h+k against the kept task's
                     // bound X[t] + misc[1] >= c (the scalar test below is the same). Only
                     // with the old-slot task kept: before that the first trial runs anyway
                     const int rem = kSlots - h;
                     const int tk = (t_start + h + lane) % kSlots;
                     const int xt = bperm(V.x, tk);                          // every lane takes part
-                    // with the pair bound of slot tk plus ei (TT_LS_P1B) when the summaries are kept
+                    // with the pair bound of slot tk plus ei when the summaries are kept
                     const int ub = TT_P1 ? pairs_lb_of(S.sinf[tk], pei, 0ull, false) : 0;
                     const bool skip = tk != t_orig && xt + S.misc[1] + ub >= eah_i + S.rp[tk];
                     const bool need = lane < rem && !skip;
@@ -126,19 +125,11 @@
                         // lb = corr_nb(ei) + corr_nb(ej) >= c = eah_i + eah_cur(ej)
                         const int rem = wrap_e(i - j + E, E);
                         // (ds_bpermute reads 0 from inactive lanes: every lane takes part)
-#if TT_LS_SLP
-                        int pk = j + lane;
-                        if (pk >= E) pk -= E;
-                        if (pk >= E) pk %= E;                      // E < 64 only
-                        const int ej = S.evl[pk], tj = S.slp[pk];
-#else
                         const int ej = S.evl[wrap_e(j + lane, E)], tj = S.sl[ej];
-#endif
                         const int xt = bperm(V.x, tj);
                         bool need = true;
                         if (lane < rem && tj != t_orig) {
                             int c1 = 0, c2 = 0, selfj = 0, cij = 0;
-#if TT_LS_ROWB
                             // ej's row 8 words at a time, all in flight before the first use
                             const uint64_t* rj = S.pb.corr64 + (size_t)ej * EW;
                             for (int w0 = 0; w0 < EW; w0 += 8) {
@@ -156,15 +147,6 @@
                                     if (w == (ei >> 6)) cij = (int)((x[k] >> (ei & 63)) & 1ull);
                                 }
                             }
-#else
-                            for (int w = 0; w < EW; ++w) {
-                                const uint64_t rw = S.pb.corr64[(size_t)ej * EW + w];
-                                c1 += __popcll(rw & S.B[(size_t)tj * EW + w]);
-                                c2 += __popcll(rw & readlane64(bo, w));
-                                if (w == (ej >> 6)) selfj = (int)((rw >> (ej & 63)) & 1ull);
-                                if (w == (ei >> 6)) cij = (int)((rw >> (ei & 63)) & 1ull);
-                            }
-#endif
                             const int c = eah_i + S.rp[tj] + c1 - selfj;
                             int lb = xt - cij + c2;
                             if (TT_P1) {                          // pair bounds of both touched slots
@@ -201,12 +183,12 @@
                             break;
                         }
                         LSP_CNT(S, kPfP1m2lb);
-                        const TaskRegs tr = load_tasks(S, 7);
+                        if (!S.listed) { list_tasks(S); S.listed = 1; }
                         if (S.nts == 2) {             // task 0 = slot(ej) plus ei, task 1 = slot(ei) plus ej
-                            if (match_tasks(S, 1, tr)) goto redo;
+                            if (match_listed_tasks(S, 1)) goto redo;
                             if (lb + S.misc[0] >= c) { LSP_CNT(S, kPfP1m2r0); restore_task<0>(S); break; }
-                            if (match_tasks(S, 2, tr)) goto redo;
-                        } else if (match_tasks(S, 7, tr)) goto redo;
+                            if (match_listed_tasks(S, 2)) goto redo;
+                        } else if (match_listed_tasks(S, 7)) goto redo;
                         const int n = lb + S.misc[task_of(S, slot_nb(S, ei))] + S.misc[task_of(S, slot_nb(S, ej))];
                         if (n < c) { LSP_CNT(S, kPfP1m2a); accept(S);
                             if (hotm) hot = refresh_hot(S, hot, false); acc = true; break; }

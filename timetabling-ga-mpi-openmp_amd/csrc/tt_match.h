@@ -21,24 +21,17 @@ namespace ttga {
 
 constexpr uint8_t kNone = 0xFF;
 
-#ifndef TT_BUCKETS_CHUNK
-#define TT_BUCKETS_CHUNK 1
-#endif
-
-// TT_ROOMS_WAVE: assign_touched matches a slot by the whole wave
-// (wave_match_slot) instead of one slot per lane (match_slot / match_slot_reg:
-// lane-serial searches that wait on LDS at every step), except the many small
-// slots of a whole-row assignment on an instance of <= 16 rooms, which stay one
-// per lane in registers; slots of more than 64 events stay lane-serial.
-#ifndef TT_ROOMS_WAVE
-#define TT_ROOMS_WAVE 1
-#endif
+// assign_touched matches a slot by the whole wave (wave_match_slot) instead of
+// one slot per lane (match_slot / match_slot_reg: lane-serial searches that wait
+// on LDS at every step), except the many small slots of a whole-row assignment
+// on an instance of <= 16 rooms, which stay one per lane in registers; slots of
+// more than 64 events stay lane-serial.
 constexpr int kWaveSlots = 8;    // touched slots up to which every slot goes to the wave matcher
 
 // Per-wave LDS scratch for one individual. Two layouts:
-//  * R <= 16 (or TT_ROOMS_WAVE=0): every slot's possible-room masks, matched
+//  * R <= 16: every slot's possible-room masks, matched
 //    rooms, room owners and dads, for one slot per lane;
-//  * R > 16 ("wide", TT_ROOMS_WAVE): the wave matcher keeps its state in
+//  * R > 16 ("wide"): the wave matcher keeps its state in
 //    registers and reads the possible rooms from the problem (L2-resident), so
 //    the scratch holds the row, its buckets and, per wave, one crowded slot's
 //    state for the lane-serial fallback: 4E + 2.4 KB per wave instead of
@@ -61,11 +54,8 @@ struct MatchScratch {
     bool wide;
 };
 
-__host__ __device__ inline bool match_wide(int R) { return TT_ROOMS_WAVE && R > 16; }
-#ifndef TT_WIDE_WAVES
-#define TT_WIDE_WAVES 4
-#endif
-constexpr int kWideWaves = TT_WIDE_WAVES;    // waves per individual in assign_rooms_kernel, wide layout
+__host__ __device__ inline bool match_wide(int R) { return R > 16; }
+constexpr int kWideWaves = 4;    // waves per individual in assign_rooms_kernel, wide layout
 
 // nw: waves sharing the individual (wide layout: one crowded slot's state each)
 __host__ __device__ inline size_t match_scratch_bytes(int E, int R, int nw = 1) {
@@ -141,10 +131,9 @@ __device__ inline void build_buckets(const DevProblem& pb, MatchScratch& m, int 
     const int start = incl - c;
     if (act && lane < kSlots) m.bstart[lane] = start;
     if (act && lane == kSlots - 1) m.bstart[kSlots] = incl;
-#if TT_BUCKETS_CHUNK
     // stable fill, 64 events at a time: each event sets its lane bit in its slot's
     // chunk mask; its place is the slot's running count plus the lower lanes of the
-    // mask (ascending event order inside a bucket, as the lane walk below)
+    // mask (ascending event order inside a bucket)
     if (act) m.cm[lane] = 0ull;
     int cur = start;                                  // lane t < 45: slot t's next position
     __syncthreads();
@@ -162,22 +151,6 @@ __device__ inline void build_buckets(const DevProblem& pb, MatchScratch& m, int 
         }
         __syncthreads();
     }
-#else
-    // stable fill: lane t walks the slot row (broadcast reads) and keeps its events
-    int pos = start;
-    int e = 0;
-    const int me = lane < kSlots ? lane : 0x100;     // lanes >= 45 never match a byte
-    for (; e + 4 <= E; e += 4) {
-        uint32_t w = (uint32_t)m.sl[e] | ((uint32_t)m.sl[e + 1] << 8) | ((uint32_t)m.sl[e + 2] << 16) |
-                     ((uint32_t)m.sl[e + 3] << 24);
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if ((int)((w >> (8 * k)) & 0xFFu) == me) m.bev[pos++] = (uint16_t)(e + k);
-    }
-    for (; e < E; ++e)
-        if (m.sl[e] == me) m.bev[pos++] = (uint16_t)e;
-    static_assert(TT_BUCKETS_CHUNK, "the lane walk has no act flag");
-#endif
     __syncthreads();
     if (m.wide || !act) return;                        // wide: the wave matcher reads pb.poss itself
     const int nb = m.bstart[kSlots];
@@ -210,10 +183,10 @@ __device__ __forceinline__ int pop_lowest(uint64_t (&f)[NW]) {
     return -1;
 }
 
-// Max-cardinality matching + read-out for one slot (N events, N <= 64*NW).
-template <int NW>
-__device__ void match_slot(int R, const uint16_t* ev, const uint64_t* pl, int N, uint8_t* mr, uint8_t* rm,
+// Max-cardinality matching + read-out for one slot (N events, N <= 64*NW = kMaxSlotEvents).
+__device__ inline void match_slot(int R, const uint16_t* ev, const uint64_t* pl, int N, uint8_t* mr, uint8_t* rm,
                            uint8_t* dr, uint8_t* rr) {
+    constexpr int NW = kMaxSlotEvents / 64;
     uint64_t unm[NW];
 #pragma unroll
     for (int w = 0; w < NW; ++w) {
@@ -293,7 +266,7 @@ __device__ void match_slot(int R, const uint16_t* ev, const uint64_t* pl, int N,
     }
 }
 
-// match_slot for N <= 32 events and R <= 16 rooms (TT_MATCH_REG) with the
+// match_slot for N <= 32 events and R <= 16 rooms with the
 // matching itself in registers: the matched room of each event as 4-bit fields
 // (mr0: events 0-15, mr1: 16-31; valid while the event's bit is clear in unm)
 // and the event matched to each room as 8-bit fields (rm0: rooms 0-7, rm1:
@@ -301,9 +274,6 @@ __device__ void match_slot(int R, const uint16_t* ev, const uint64_t* pl, int N,
 // possible rooms (and writes its dads there, read back on the augmenting path):
 // a room expansion and the path's matched-room lookups are register selects.
 // Same search, same result as match_slot.
-#ifndef TT_MATCH_REG
-#define TT_MATCH_REG 1
-#endif
 __device__ __forceinline__ uint32_t nib_get(uint64_t w0, uint64_t w1, int i) {
     return (uint32_t)(((i < 16 ? w0 : w1) >> (4 * (i & 15))) & 15ull);
 }
@@ -498,7 +468,6 @@ __device__ __forceinline__ uint32_t wave_match_slot(int R, int N, uint64_t pl, i
 // wave w of nw: the slots t with t % nw == w (wide layout only).
 __device__ inline void assign_touched(const DevProblem& pb, MatchScratch& m, uint64_t touched, int lane,
                                       int w = 0, int nw = 1) {
-#if TT_ROOMS_WAVE
     const int R = pb.R;
     touched &= (1ull << kSlots) - 1ull;
     if (nw > 1) {                                       // this wave's slots: t % nw == w
@@ -550,32 +519,13 @@ __device__ inline void assign_touched(const DevProblem& pb, MatchScratch& m, uin
                 uint8_t* sdr = m.wide ? m.dr + w * R : m.dr + tc * R;
                 if (m.wide)
                     for (int i = 0; i < Nc; ++i) spl[i] = pb.poss[m.bev[bc + i]];
-                match_slot<4>(R, m.bev + bc, spl, Nc, smr, srm, sdr, m.rr);
+                match_slot(R, m.bev + bc, spl, Nc, smr, srm, sdr, m.rr);
             }
         } else {
             for (int i = lane; i < Nc; i += 64) m.rr[m.bev[bc + i]] = 0xFF;
             if (lane == 0) atomicOr(pb.status, 1);
         }
     }
-#else
-    if (lane < kSlots && ((touched >> lane) & 1ull)) {
-        const int b0 = m.bstart[lane];
-        const int N = m.bstart[lane + 1] - b0;
-        const int R = pb.R;
-        if (N > 0) {
-            if (TT_MATCH_REG && N <= 32 && R <= 16)
-                match_slot_reg(m.bev + b0, m.pl + b0, N, m.dr + lane * R, m.rr);
-            else if (N <= 64)
-                match_slot<1>(R, m.bev + b0, m.pl + b0, N, m.mr + b0, m.rm + lane * R, m.dr + lane * R, m.rr);
-            else if (N <= kMaxSlotEvents)
-                match_slot<4>(R, m.bev + b0, m.pl + b0, N, m.mr + b0, m.rm + lane * R, m.dr + lane * R, m.rr);
-            else {
-                for (int i = 0; i < N; ++i) m.rr[m.bev[b0 + i]] = 0xFF;
-                atomicOr(pb.status, 1);
-            }
-        }
-    }
-#endif
     __syncthreads();
 }
 

@@ -9,9 +9,6 @@
 namespace ttga {
 
 constexpr int kMaxRejections = 1 << 20;
-#ifndef TT_ROOMS_ABL
-#define TT_ROOMS_ABL 0
-#endif
 
 // ---------------------------------------------------------------- helpers
 // 512 bytes per block: the block's eight loads are all in flight before the
@@ -55,9 +52,7 @@ __global__ __launch_bounds__(64 * kWideWaves) void assign_rooms_kernel(DevProble
     }
     __syncthreads();
     build_buckets(pb, m, lane, w == 0);
-#if TT_ROOMS_ABL != 1                                    // profiling builds only: buckets alone
     assign_touched(pb, m, ~0ull, lane, w, nw);
-#endif
     if (w == 0) store_row(room + p * E, m.rr, E, lane);
 }
 

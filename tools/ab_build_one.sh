@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B build of ONE source file of the working tree with extra flags
 # (HIPX), linked with the in-tree objects of the others (make first):
-#   HIPX=-DTT_T5_PRIO=1 tools/ab_build_one.sh tt_eval prio
+#   HIPX=-DTT_LS_PROF tools/ab_build_one.sh tt_ls prof
 set -eu
 REPO=$(cd "$(dirname "$0")/.." && pwd)
 SRC=$1; NAME=$2
