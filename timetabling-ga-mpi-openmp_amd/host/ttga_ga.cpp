@@ -11,6 +11,11 @@
 //
 //   ttga-ga -i instance.tim [-s seed] [-p type] [-c children]
 //           [-p1 x -p2 y -p3 z] [--gpus G] [--islands K] [--pop N] [--generations n] [--rccl] [--stagger]
+//           [--report]
+//
+// --report: after the solution lines, one `report` line per island: the best
+// member's six constraint parts, their sums over the population and its slot
+// diversity (include/ttga_report.h; the same line as ttga/report.py prints).
 //
 // --stagger / --stagger-parts P: the children of a generation are 2 / P
 // sub-batches on as many streams, sub-batch h bred from the population after
@@ -56,7 +61,7 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/ttga.h"
+#include "../../include/ttga_report.h"
 
 namespace {
 
@@ -88,6 +93,7 @@ struct Control {
     int gpus = 1, islands = 0, pop = 10, generations = -1;
     bool rccl = false;
     int stagger = 0;                              // sub-batches of the staggered schedule (0: batch)
+    bool report = false;                          // a population report line per island
 };
 
 // Control::Control (Control.cpp:3-137) plus the --gpus/--pop/--generations extensions.
@@ -100,6 +106,10 @@ Control parse_control(int argc, char** argv) {
     }
     if (auto it = std::find(args.begin(), args.end(), "--stagger"); it != args.end()) {
         c.stagger = 2;
+        args.erase(it);
+    }
+    if (auto it = std::find(args.begin(), args.end(), "--report"); it != args.end()) {
+        c.report = true;
         args.erase(it);
     }
     for (const char* k : {"--gpus", "--islands", "--pop", "--generations", "--children", "--stagger-parts"}) {
@@ -351,6 +361,52 @@ int replay_log(const char* path) {
     return 0;
 }
 
+// --report (ttga/report.py population_report + report_line) from the host copies
+// of tt_eval_parts' parts[N][6] and tt_slot_histogram's hist[E][45]
+Json report_line(const std::vector<int32_t>& parts, const std::vector<int32_t>& hist, int N, int E, int proc,
+                 int island) {
+    static const char* const kNames[TT_NUM_PARTS] = {"room_pairs", "corr_pairs", "unsuitable",
+                                                     "last_slot", "consecutive", "single_class"};
+    long sum[TT_NUM_PARTS] = {0}, nonzero[TT_NUM_PARTS] = {0}, valid = 0, feasible = 0;
+    for (int i = 0; i < N; i++) {
+        const int32_t* r = &parts[(size_t)i * TT_NUM_PARTS];
+        if (r[0] < 0) continue;
+        valid++;
+        feasible += r[0] + r[1] + r[2] == 0;
+        for (int k = 0; k < TT_NUM_PARTS; k++) { sum[k] += r[k]; nonzero[k] += r[k] != 0; }
+    }
+    long long differing = 0;
+    for (int e = 0; e < E; e++) {
+        long long n = 0, sq = 0;
+        for (int t = 0; t < TT_NUM_SLOTS; t++) {
+            const long long h = hist[(size_t)e * TT_NUM_SLOTS + t];
+            n += h;
+            sq += h * h;
+        }
+        differing += n * n - sq;
+    }
+    Json best, psum, pnz, popu, div, rep;
+    for (int k = 0; k < TT_NUM_PARTS; k++) {
+        best.obj[kNames[k]] = Json::I(parts[k]);
+        psum.obj[kNames[k]] = Json::I(sum[k]);
+        pnz.obj[kNames[k]] = Json::I(nonzero[k]);
+    }
+    popu.obj["size"] = Json::I(N);
+    popu.obj["feasible"] = Json::I(feasible);
+    popu.obj["invalid"] = Json::I(N - valid);
+    popu.obj["sum"] = psum;
+    popu.obj["nonzero"] = pnz;
+    div.obj["events"] = Json::I(E);
+    div.obj["size"] = Json::I(N);
+    div.obj["pairs_differing"] = Json::I((long)(differing / 2));
+    rep.obj["best"] = best;
+    rep.obj["population"] = popu;
+    rep.obj["diversity"] = div;
+    rep.obj["procID"] = Json::I(proc);
+    rep.obj["island"] = Json::I(island);
+    return wrap("report", rep);
+}
+
 // ---------------------------------------------------------------- islands
 struct Pop {
     int n = 0, E = 0;
@@ -600,6 +656,23 @@ struct Island {
         if (cost.offer(m.feasible, m.scv, m.hcv, entry)) out.line(log_line(entry, id, thread, seconds_since(t0)));
     }
 
+    // the --report line of the population with every sub-batch replaced
+    Json report(int proc, int island) {
+        flush();
+        int32_t *d_parts = nullptr, *d_hist = nullptr;
+        std::vector<int32_t> parts((size_t)N * TT_NUM_PARTS), hist((size_t)E * TT_NUM_SLOTS);
+        check_hip(hipMalloc(&d_parts, 4 * parts.size()), "hipMalloc");
+        check_hip(hipMalloc(&d_hist, 4 * hist.size()), "hipMalloc");
+        check_tt(tt_eval_parts(tp, pop.slot, pop.room, N, d_parts, nullptr, st), "tt_eval_parts");
+        check_tt(tt_slot_histogram(tp, pop.slot, N, d_hist, st), "tt_slot_histogram");
+        check_hip(hipMemcpyAsync(parts.data(), d_parts, 4 * parts.size(), hipMemcpyDeviceToHost, st), "hipMemcpy");
+        check_hip(hipMemcpyAsync(hist.data(), d_hist, 4 * hist.size(), hipMemcpyDeviceToHost, st), "hipMemcpy");
+        check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
+        (void)hipFree(d_parts);
+        (void)hipFree(d_hist);
+        return report_line(parts, hist, N, E, proc, island);
+    }
+
     // serializeSolutions(k, 1, ...) (ga.cpp:318-342) into send_buf
     void pack(int k, uint8_t* send_buf) {
         auto cp = [&](void* dst, const void* src, size_t n) {
@@ -810,6 +883,11 @@ int main(int argc, char** argv) {
         check_hip(hipMemcpy(rm.data(), I.pop.room, I.E, hipMemcpyDeviceToHost), "hipMemcpy");
         out.line(solution_line(b.feasible, b.scv, b.hcv, sl, rm, k, seconds_since(t_begin)));
     }
+    if (ctl.report)
+        for (int k = 0; k < K; k++) {
+            check_hip(hipSetDevice(isl[k].device), "hipSetDevice");
+            out.line(isl[k].report(k, k));
+        }
     out.line(run_final_line(K, C, seconds_since(t_start)));
     for (int k = 0; k < K; k++) {
         (void)hipSetDevice(isl[k].device);

@@ -313,6 +313,14 @@ class Island(Members):
         self.sync()
         return super().member_meta(k)
 
+    def report(self) -> dict:
+        """ttga.report.population_report of the island's population, on the
+        island's stream, with every pending sub-batch replaced first."""
+        from .report import population_report
+        self.flush()
+        with self._on_stream():
+            return population_report(self.dp, self.pop)
+
     def _evaluate(self, p):
         self.dp.eval(p["slot"], p["room"], out=(p["hcv"], p["scv"], p["feasible"], p["penalty"]))
 

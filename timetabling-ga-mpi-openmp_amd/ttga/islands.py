@@ -12,6 +12,9 @@ Reference correspondence:
   ga.cpp (every JSON line goes to stdout, ga.cpp:60). `-c` (threads) sets the
   children bred per generation. Extensions: `--pop N` (ga.cpp:64 has 10,
   N >= 3), `--islands K` (islands per process, default 1), `--generations G`,
+  `--report` (after the solution lines, one `report` line per island of the
+  process: the best member's six constraint parts, their sums over the
+  population and its slot diversity, ttga.report),
   `--stagger` / `--stagger-parts P` (the children of a generation as 2 / P
   sub-batches on as many streams, each bred P - 1 sub-batches behind:
   ttga.ga.Island's staggered schedule),
@@ -54,6 +57,9 @@ def parse_control(argv, out=sys.stdout, err=sys.stderr) -> dict:
     if "--stagger" in args:               # the staggered schedule (ttga.ga.Island), 2 sub-batches
         args.remove("--stagger")
         extra["stagger"] = 2
+    if "--report" in args:                # a population report line per island (ttga.report)
+        args.remove("--report")
+        extra["report"] = True
     for k in ("--pop", "--children", "--generations", "--islands", "--stagger-parts"):
         if k in args:
             i = args.index(k)
@@ -297,6 +303,10 @@ def main(argv=None):
         out.write(run_best_line(vals[0][0], gmin) + "\n")
     for k, isl in enumerate(islands):
         out.write(solution_line(isl.member(0), rank * K + k, time.perf_counter() - t_begin) + "\n")
+    if ctl.get("report"):
+        from .report import report_line
+        for k, isl in enumerate(islands):
+            out.write(report_line(isl.report(), rank * K + k, k) + "\n")
     out.flush()
     if use_dist:
         dist.barrier()

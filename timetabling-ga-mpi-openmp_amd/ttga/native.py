@@ -27,6 +27,10 @@ EXPORTS = (
     "tt_local_search_stats", "tt_local_search_masks", "tt_local_search_eval",
 )
 
+# include/ttga_report.h
+REPORT_EXPORTS = ("tt_eval_parts", "tt_slot_histogram")
+PART_NAMES = ("room_pairs", "corr_pairs", "unsuitable", "last_slot", "consecutive", "single_class")
+
 _lib = None
 
 
@@ -74,6 +78,10 @@ def load(path: os.PathLike | str | None = None) -> ctypes.CDLL:
     lib.tt_last_error.restype = ctypes.c_char_p
     lib.tt_last_error.argtypes = []
     lib.tt_version.argtypes = []
+    lib.tt_eval_parts.argtypes = [vp, vp, vp, i32, vp, vp, vp]
+    lib.tt_slot_histogram.argtypes = [vp, vp, i32, vp, vp]
+    for name in REPORT_EXPORTS:
+        getattr(lib, name).restype = ctypes.c_int
     for name in EXPORTS:
         if name not in ("tt_last_error", "tt_ga_work_bytes", "tt_ga_work_source_offset"):
             getattr(lib, name).restype = ctypes.c_int
@@ -164,6 +172,32 @@ class DeviceProblem:
                                                   scv.data_ptr(), feas.data_ptr(), pen.data_ptr(), variant,
                                                   self._stream(slot)))
         return out
+
+    def eval_parts(self, slot, room, event_hcv: bool = False, out=None):
+        """tt_eval_parts: the six constraint parts (PART_NAMES order) of every
+        individual as an int32 [P, 6] tensor (`out`, if given); with event_hcv
+        also Solution::eventHcv of every event, int32 [P, E]."""
+        import torch
+        P = self._pop(slot, room)
+        if out is None:
+            out = torch.empty((P, len(PART_NAMES)), dtype=torch.int32, device=slot.device)
+        elif not (out.is_cuda and out.dtype == torch.int32 and out.is_contiguous()
+                  and tuple(out.shape) == (P, len(PART_NAMES)) and out.device == slot.device):
+            raise ValueError("out must be a contiguous int32 CUDA tensor of shape [P, 6] on the population's device")
+        eh = torch.empty((P, self.E), dtype=torch.int32, device=slot.device) if event_hcv else None
+        _check(self.lib, self.lib.tt_eval_parts(self.handle, slot.data_ptr(), room.data_ptr(), P, out.data_ptr(),
+                                                ctypes.c_void_p(eh.data_ptr() if event_hcv else None),
+                                                self._stream(slot)))
+        return (out, eh) if event_hcv else out
+
+    def slot_histogram(self, slot):
+        """tt_slot_histogram: int32 [E, 45], the individuals with each event in each slot."""
+        import torch
+        P = self._pop(slot)
+        hist = torch.empty((self.E, NUM_SLOTS), dtype=torch.int32, device=slot.device)
+        _check(self.lib, self.lib.tt_slot_histogram(self.handle, slot.data_ptr(), P, hist.data_ptr(),
+                                                    self._stream(slot)))
+        return hist
 
     def assign_rooms(self, slot, room=None):
         import torch
