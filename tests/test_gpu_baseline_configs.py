@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 import ttga
+from helpers import dev, host
 from oracle_lib import oracle, ref, split_rows
 
 pytestmark = pytest.mark.gpu
@@ -29,15 +30,6 @@ from ttga import native  # noqa: E402
 from ttga.ga import Island, stream_seeds  # noqa: E402
 
 KEYS = ("slot", "room", "hcv", "scv", "feasible", "penalty")
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
 
 
 @pytest.fixture(scope="module")

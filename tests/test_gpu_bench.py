@@ -9,6 +9,8 @@ import sys
 
 import pytest
 
+from helpers import free_port as _free_port
+
 pytestmark = pytest.mark.gpu
 
 REPO = pathlib.Path(__file__).resolve().parent.parent
@@ -65,13 +67,6 @@ def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
         got = np.load(tmp_path / f"{name}.npy")
         assert got.dtype == np.float64 and got.shape == (P,)
         assert np.array_equal(got, want.astype(np.float64)), name
-
-
-def _free_port() -> int:
-    import socket
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
 
 
 def test_bench_two_ranks_rehearsal():

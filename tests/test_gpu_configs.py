@@ -13,7 +13,6 @@
 import json
 import os
 import pathlib
-import socket
 import subprocess
 import sys
 
@@ -21,6 +20,7 @@ import numpy as np
 import pytest
 
 import ttga
+from helpers import dev, free_port as _free_port, host, oracle_population
 from oracle_lib import oracle
 
 pytestmark = pytest.mark.gpu
@@ -33,15 +33,6 @@ from ttga.islands import broadcast_population, rank_seed, ring_migrate  # noqa: 
 REPO = pathlib.Path(__file__).resolve().parent.parent
 KEYS = ("slot", "room", "hcv", "scv", "feasible", "penalty")
 CONFIGS = ["lg"] + [f"comp{k:02d}" for k in range(1, 21)]
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
 
 
 @pytest.fixture(scope="module")
@@ -132,14 +123,6 @@ def test_invalid_genome_ranks_last(orc):
 
 
 # ---------------------------------------------------------------- island model
-def oracle_population(o, N, seed, steps):
-    s, r, g = o.random_init(stream_seeds(seed, 0, N))
-    s, r, g = o.local_search(s, r, g, steps)
-    h, sc, f, p = o.eval(s, r)
-    pop = dict(slot=s, room=r, hcv=h, scv=sc, feasible=f, penalty=p)
-    return o.ga_replace(pop, {k: v[:0] for k, v in pop.items()})
-
-
 def oracle_islands(o, W, N, C, gens, seed, steps):
     """The island model restated over the oracle's primitives: island g has
     seed abs(seed + g*(seed/10)) (ga.cpp:412) and starts from island 0's
@@ -311,12 +294,6 @@ def test_rccl_one_rank_drivers_lg(tmp_path):
     from test_gpu_ga import assert_validated
     for v in runs.values():
         assert_validated(inst, tim, v)
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
 
 
 def test_islands_two_ranks_gloo_one_gpu(tmp_path):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import ttga
+from helpers import dev, host, json_lines as _json_lines, oracle_population
 from oracle_lib import oracle
 
 pytestmark = pytest.mark.gpu
@@ -19,24 +20,6 @@ from ttga.ga import Island, stream_seeds  # noqa: E402
 
 REPO = pathlib.Path(__file__).resolve().parent.parent
 KEYS = ("slot", "room", "hcv", "scv", "feasible", "penalty")
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
-
-
-def oracle_population(o, N, seed, steps):
-    s, r, g = o.random_init(stream_seeds(seed, 0, N))
-    s, r, g = o.local_search(s, r, g, steps)
-    h, sc, f, p = o.eval(s, r)
-    pop = dict(slot=s, room=r, hcv=h, scv=sc, feasible=f, penalty=p)
-    empty = {k: v[:0] for k, v in pop.items()}
-    return o.ga_replace(pop, empty)
 
 
 @pytest.fixture(scope="module")
@@ -273,19 +256,6 @@ def assert_validated(inst, tim, stdout):
     chk = REPO / "timetabling-ga-mpi-openmp_amd" / "ttga-check"
     out = subprocess.run([str(chk), str(tim), "-"], input=stdout, capture_output=True, text=True, timeout=60)
     assert out.returncode == 0, out.stdout
-
-
-def _json_lines(text):
-    """JSON lines with the wall-clock fields removed."""
-    out = []
-    for ln in text.splitlines():
-        if ln.startswith("{"):
-            obj = json.loads(ln)
-            for v in obj.values():
-                v.pop("time", None)
-                v.pop("totalTime", None)
-            out.append(obj)
-    return out
 
 
 def test_native_driver_matches_python_driver(tmp_path, sm):

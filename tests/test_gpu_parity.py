@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import ttga
+from helpers import dev, host
 from oracle_lib import oracle
 
 pytestmark = pytest.mark.gpu
@@ -22,15 +23,6 @@ def load(golden_dir, name):
     E, R, F, S = (int(x) for x in z["dims"])
     inst = ttga.Instance(E, R, F, S, z["room_size"], z["student_events"], z["room_features"], z["event_features"])
     return inst, z
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
 
 
 @pytest.fixture(scope="module")

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import ttga
+from helpers import dev, host
 from oracle_lib import oracle
 from ttga import validate
 
@@ -24,15 +25,6 @@ from ttga.report import population_report  # noqa: E402
 NAMES = ["sm", "med", "tight"]
 SHAPES = [(65, 1, 2, 30), (333, 9, 6, 170), (448, 11, 5, 300), (449, 10, 5, 200), (250, 64, 4, 120)]
 WIDE = [(1000, 20, 6, 700), (2600, 12, 5, 150)]
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
 
 
 def load(golden_dir, name):

@@ -1,7 +1,6 @@
 """--report in both GA drivers (python -m ttga.islands, ttga-ga): the same
 report lines from both, nothing else changed in the output, and the best
 member's parts reproduce the solution line."""
-import json
 import os
 import pathlib
 import subprocess
@@ -10,6 +9,7 @@ import sys
 import pytest
 
 import ttga
+from helpers import json_lines as _json_lines
 from ttga import native, validate
 
 pytestmark = pytest.mark.gpu
@@ -17,19 +17,6 @@ torch = pytest.importorskip("torch")
 
 REPO = pathlib.Path(__file__).resolve().parent.parent
 PKG = REPO / "timetabling-ga-mpi-openmp_amd"
-
-
-def _json_lines(text):
-    """JSON lines with the wall-clock fields removed."""
-    out = []
-    for ln in text.splitlines():
-        if ln.startswith("{"):
-            obj = json.loads(ln)
-            for v in obj.values():
-                v.pop("time", None)
-                v.pop("totalTime", None)
-            out.append(obj)
-    return out
 
 
 def _raw_report_lines(text):

@@ -3,13 +3,14 @@ reference's JSON line format, and the island-model communication over gloo
 with world_size 2 (ring migration ga.cpp:479-540, MIN reduce ga.cpp:234-257)."""
 import io
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
+
+from helpers import free_port as _free_port
 
 from ttga.ga import json_line, max_steps_for, stream_seeds
 from ttga.islands import global_min, parse_control, rank_seed, ring_migrate
@@ -74,12 +75,6 @@ def _worker(rank, world, K, port, q):
     q.put((rank, before, [snapshot(i) for i in isl], m))
     dist.barrier()
     dist.destroy_process_group()
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
 
 
 def test_ring_migration_local_islands():

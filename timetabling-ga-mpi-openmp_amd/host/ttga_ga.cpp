@@ -463,15 +463,17 @@ struct Island {
     uint8_t *send_best = nullptr, *send_second = nullptr, *recv_buf = nullptr;
     size_t migrant_bytes = 0;
     CostState cost;                                   // setCurrentCost state (ga.cpp:163-167)
-    // staggered schedule (ttga.ga.Island schedule "staggered"): part j of the child
-    // rows [off, off + n) on stream hs[j] with its own work buffer; every population
-    // operation (breed or replace) waits for the previous one (ev_op), so sub-batch h
-    // is bred after the replacement of h - parts and h - parts + 1 is replaced after
-    // the breed of h
+    // the generation's pipeline (ttga.ga.Island): part j of the child rows [off, off + n)
+    // on stream s with its own work buffer; every population operation (breed or replace)
+    // follows the previous one, so sub-batch h is bred after the replacement of h - parts
+    // and h - parts + 1 is replaced after the breed of h. parts == 1 (no --stagger) is the
+    // batch schedule: part[0] = {0, C, st, work}, each sub-batch replaced behind its own
+    // search, and neither ev_op nor another stream or work buffer exists
     int parts = 1;
     struct Part { int off = 0, n = 0; hipStream_t s = nullptr; void* work = nullptr; };
     std::vector<Part> part;
-    hipEvent_t ev_op = nullptr;
+    hipEvent_t ev_op = nullptr;                       // behind the last population operation (parts > 1)
+    hipStream_t op_stream = nullptr;                  // the stream that operation ran on
     std::vector<int> pending;                         // parts searched, not yet replaced (breed order)
     int last_replace = 0;
 
@@ -497,23 +499,31 @@ struct Island {
         check_hip(hipMalloc(&send_best, migrant_bytes), "hipMalloc");
         check_hip(hipMalloc(&send_second, migrant_bytes), "hipMalloc");
         check_hip(hipMalloc(&recv_buf, 2 * migrant_bytes), "hipMalloc");
-        if (parts > 1) {
-            check_hip(hipEventCreateWithFlags(&ev_op, hipEventDisableTiming), "hipEventCreate");
-            part.resize(parts);
-            for (int j = 0, off = 0; j < parts; j++) {          // numpy.array_split's sizes
-                const int n = C / parts + (j < C % parts ? 1 : 0);
-                part[j].off = off;
-                part[j].n = n;
-                off += n;
-                if (j == 0) {
-                    part[j].s = st;
-                    part[j].work = work;
-                } else {
-                    check_hip(hipStreamCreateWithFlags(&part[j].s, hipStreamNonBlocking), "hipStreamCreate");
-                    check_hip(hipMalloc(&part[j].work, std::max<size_t>(tt_ga_work_bytes(N, E), 16)), "hipMalloc");
-                }
+        if (parts > 1) check_hip(hipEventCreateWithFlags(&ev_op, hipEventDisableTiming), "hipEventCreate");
+        op_stream = st;
+        part.assign(parts, Part{0, 0, st, work});
+        for (int j = 0, off = 0; j < parts; j++) {              // numpy.array_split's sizes
+            part[j].off = off;
+            part[j].n = C / parts + (j < C % parts ? 1 : 0);
+            off += part[j].n;
+            if (j > 0) {
+                check_hip(hipStreamCreateWithFlags(&part[j].s, hipStreamNonBlocking), "hipStreamCreate");
+                check_hip(hipMalloc(&part[j].work, std::max<size_t>(tt_ga_work_bytes(N, E), 16)), "hipMalloc");
             }
         }
+    }
+
+    // All cross-stream ordering: what s runs next comes after the last population
+    // operation (nothing to do when that ran on s, as it always did with one part) ...
+    void wait_op(hipStream_t s) {
+        if (s != op_stream) check_hip(hipStreamWaitEvent(s, ev_op, 0), "hipStreamWaitEvent");
+    }
+
+    // ... and a population operation (breed, replace, or a write of the population by
+    // the caller: the initial broadcast, the migrants) has just been enqueued on s
+    void wrote_population(hipStream_t s) {
+        op_stream = s;
+        if (parts > 1) check_hip(hipEventRecord(ev_op, s), "hipEventRecord");
     }
 
     void evaluate(Pop& p, hipStream_t s = nullptr) {
@@ -529,7 +539,7 @@ struct Island {
         check_tt(tt_ga_replace(tp, pop.slot, pop.room, pop.hcv, pop.scv, pop.feasible, pop.penalty, N, pop.slot,
                                pop.room, pop.hcv, pop.scv, pop.feasible, pop.penalty, 0, work, st),
                  "tt_ga_replace");
-        if (parts > 1) check_hip(hipEventRecord(ev_op, st), "hipEventRecord");
+        wrote_population(st);
     }
 
     // children rows [off, off + n) as a population view
@@ -574,48 +584,45 @@ struct Island {
                  "tt_ga_replace");
     }
 
-    // one generation of C children (ga.cpp:543-585)
+    // one generation of C children (ga.cpp:543-585): each sub-batch in turn
     void step() {
-        if (parts > 1) {
-            for (int j = 0; j < parts; j++) part_step(j);
-            return;
-        }
-        breed(0, C, st);
-        search(0, C, st, work);
-        replace(0, C, st, work);
+        for (int j = 0; j < parts; j++) advance(j);
     }
 
-    void part_step(int j) {
+    // sub-batch j: bred behind the last population operation; with parts - 1 older
+    // sub-batches pending, the oldest is replaced behind that breed; then j is searched
+    // (one part: and replaced at once, the sub-batch parts - 1 behind being itself)
+    void advance(int j) {
         const Part& p = part[j];
-        check_hip(hipStreamWaitEvent(p.s, ev_op, 0), "hipStreamWaitEvent");      // breed(h) after replace(h - parts)
+        wait_op(p.s);                                                            // breed(h) after replace(h - parts)
         breed(p.off, p.n, p.s);
-        check_hip(hipEventRecord(ev_op, p.s), "hipEventRecord");
-        if ((int)pending.size() >= parts - 1) replace_oldest();                 // replace(h - parts + 1) after breed(h)
+        wrote_population(p.s);
+        if (!pending.empty() && (int)pending.size() >= parts - 1) replace_oldest();   // replace(h - parts + 1) after breed(h)
         search(p.off, p.n, p.s, p.work);
         pending.push_back(j);
+        if ((int)pending.size() >= parts) replace_oldest();
     }
 
     void replace_oldest() {
         const int j = pending.front();
         pending.erase(pending.begin());
         const Part& p = part[j];
-        check_hip(hipStreamWaitEvent(p.s, ev_op, 0), "hipStreamWaitEvent");
+        wait_op(p.s);
         replace(p.off, p.n, p.s, p.work);
-        check_hip(hipEventRecord(ev_op, p.s), "hipEventRecord");
+        wrote_population(p.s);
         last_replace = j;
     }
 
-    // staggered: replace the pending sub-batches; st then follows the population's last operation
+    // replace the pending sub-batches; st then follows the population's last operation
     void flush() {
-        if (parts <= 1) return;
         while (!pending.empty()) replace_oldest();
-        check_hip(hipStreamWaitEvent(st, ev_op, 0), "hipStreamWaitEvent");
+        wait_op(st);
     }
 
     // pop[k]'s fields, read behind the last replacement enqueued (staggered: the
     // pending half-batch stays pending, as ttga.ga.Island.snapshot)
     Member member_now(int k) {
-        const hipStream_t s = parts > 1 ? part[last_replace].s : st;
+        const hipStream_t s = part[last_replace].s;
         Member m{};
         uint8_t f = 0;
         check_hip(hipMemcpyAsync(&f, pop.feasible + k, 1, hipMemcpyDeviceToHost, s), "hipMemcpy");
@@ -638,15 +645,14 @@ struct Island {
     // tt_ga_work_source_offset in its work buffer), else 0
     int best_thread(bool after_step) {
         if (!after_step) return 0;
-        const hipStream_t s = parts > 1 ? part[last_replace].s : st;
-        const void* w = parts > 1 ? part[last_replace].work : work;
-        const int base = parts > 1 ? part[last_replace].off : 0, nb = parts > 1 ? part[last_replace].n : C;
+        const Part& p = part[last_replace];
         int32_t src = 0;
-        check_hip(hipMemcpyAsync(&src, (const uint8_t*)w + tt_ga_work_source_offset(N, E), 4, hipMemcpyDeviceToHost, s),
+        check_hip(hipMemcpyAsync(&src, (const uint8_t*)p.work + tt_ga_work_source_offset(N, E), 4,
+                                 hipMemcpyDeviceToHost, p.s),
                   "hipMemcpy");
-        check_hip(hipStreamSynchronize(s), "hipStreamSynchronize");
-        const long k = N - nb;
-        return src >= k && src < N ? (int)(base + src - k) : 0;
+        check_hip(hipStreamSynchronize(p.s), "hipStreamSynchronize");
+        const long k = N - p.n;
+        return src >= k && src < N ? (int)(p.off + src - k) : 0;
     }
 
     // setCurrentCost (ga.cpp:203-228) on pop[0] as the last replacement left it
@@ -697,7 +703,7 @@ struct Island {
         cp(pop.scv + pos, buf + 2 * E + 4, 4);
         cp(pop.penalty + pos, buf + 2 * E + 8, 4);
         cp(pop.feasible + pos, buf + 2 * E + 12, 1);
-        if (parts > 1) check_hip(hipEventRecord(ev_op, st), "hipEventRecord");   // the next breed sees the migrants
+        wrote_population(st);                                  // the next breed sees the migrants
     }
 
     void release() {
@@ -803,7 +809,7 @@ int main(int argc, char** argv) {
             cp(I.pop.penalty, z.penalty, 4 * (size_t)N);
             cp(I.pop.feasible, z.feasible, (size_t)N);
         }
-        if (I.parts > 1) check_hip(hipEventRecord(I.ev_op, I.st), "hipEventRecord");   // the shared population
+        I.wrote_population(I.st);                     // the shared population
         sync(I);
         barrier.wait();
         if (k == 0) t_begin = std::chrono::steady_clock::now();      // beginTry (ga.cpp:476)

@@ -20,9 +20,11 @@ Stream k of an island with seed s starts at Random(|s| + 1 + k).
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import math
 import time
+import types
 
 import numpy as np
 
@@ -137,6 +139,7 @@ class Members:
 
 
 _SIDE_STREAMS: dict = {}
+_NO_STREAM = contextlib.nullcontext()     # work on torch's current stream
 
 
 def _side_streams(dev, base, n: int) -> list:
@@ -156,26 +159,30 @@ def _side_streams(dev, base, n: int) -> list:
 class Island(Members):
     """One island: population [N] + C child slots, all device-resident.
 
-    schedule "batch": a generation breeds all C children from the population,
-    searches them in one launch and replaces the C worst (the next generation
-    waits for the slowest child). schedule "staggered": the child slots are
-    split into `parts` sub-batches (part j: child slots [j*C/parts, ...) rounded
-    as numpy.array_split) on as many streams, and sub-batch h is bred from the
-    population after the replacement of sub-batch h - parts, so sub-batch h's
-    local search runs while the searches of h - parts + 1 .. h - 1 finish. The
-    population operations are totally ordered -- breed(h) after replace(h -
-    parts), replace(h - parts + 1) after breed(h) -- so results are
-    deterministic, and C children are in flight at every breed, as in the batch
-    schedule and as with ga.cpp:488-588's C threads breeding from the shared
+    The child slots are split into `parts` sub-batches (part j: child slots
+    [j*C/parts, ...) rounded as numpy.array_split) on as many streams, and
+    sub-batch h is bred from the population after the replacement of sub-batch
+    h - parts, so sub-batch h's local search runs while the searches of
+    h - parts + 1 .. h - 1 finish. The population operations are totally
+    ordered -- breed(h) after replace(h - parts), replace(h - parts + 1) after
+    breed(h) -- so results are deterministic, and C children are in flight at
+    every breed, as with ga.cpp:488-588's C threads breeding from the shared
     population while the other threads' children are still searched. step()
     advances `parts` sub-batches and leaves parts - 1 of them pending; flush()
     replaces them (every host read of the population flushes first; the
-    snapshots the drivers log from do not). The parts run on streams of their
-    own even when the island's stream is None; initialize(), step() and
-    flush() order their population operations after the caller's work on its
-    stream (the island's, else torch's current stream) and make that stream
-    wait for the last of them, so the caller's next reads and writes of the
-    population are ordered as on a batch island.
+    snapshots the drivers log from do not).
+
+    schedule "batch" is the pipeline with one part: all C children, on the
+    island's stream (None: torch's current stream at each call), with
+    self.work; a generation breeds them, searches them in one launch and
+    replaces the C worst (sub-batch h - parts + 1 is h itself), nothing stays
+    pending, and no other stream or event exists. schedule "staggered" is
+    `parts` >= 2: the parts run on streams of their own even when the island's
+    stream is None; initialize(), step() and flush() order their population
+    operations after the caller's work on its stream (the island's, else
+    torch's current stream) and make that stream wait for the last of them, so
+    the caller's next reads and writes of the population are ordered as on a
+    one-part island.
     """
 
     def __init__(self, dp, pop_size: int = 10, children: int = 1, max_steps: int = 200, seed: int = 1,
@@ -210,49 +217,46 @@ class Island(Members):
         self.rng_child = torch.from_numpy(stream_seeds(seed, self.N, self.C)).to(dev)
         self.work = dp.ga_work(self.N)
         self.generation = 0
+        self.schedule = schedule
+        self.parts = int(parts) if schedule == "staggered" else 1
         self._user_stream = stream                    # None: torch's current stream at each call
-        if schedule == "staggered" and stream is None:
+        if self.parts > 1 and stream is None:
             # every part on a stream of its own, the first included: work on the legacy
             # null stream orders itself against the other streams' work, which would
             # serialise the parts (profiles/r06_n_trace_overlap_comp20_staggered.json)
             stream = _side_streams(dev, None, 1)[0]
         self.stream = stream
-        self.schedule = schedule
-        self.parts = int(parts) if schedule == "staggered" else 1
+        # part j: child rows [off, off + n) as views of the child, rng_child and flags tensors,
+        # a work buffer and a stream; part 0 runs on the island's stream with self.work, the
+        # others on streams and buffers of their own
+        bounds = [0] + [int(b) for b in np.cumsum([len(x) for x in np.array_split(np.arange(self.C), self.parts)])]
+        streams = [stream] + _side_streams(dev, stream, self.parts - 1)
+        self._parts = []
+        for j, st in enumerate(streams):
+            r = slice(bounds[j], bounds[j + 1])
+            self._parts.append(types.SimpleNamespace(
+                off=r.start, n=r.stop - r.start, child={k: v[r] for k, v in self.child.items()}, rng=self.rng_child[r],
+                flags=self.flags[r], work=self.work if j == 0 else dp.ga_work(self.N), stream=st))
+        self._pending = []                            # parts searched but not yet replaced, in breed order
+        self._last_replace = 0                        # part whose work buffer holds the last replace's source
+        # the last population operation (breed or replace): the stream it ran on, and (several
+        # parts) the event recorded behind it, which the next one waits for on another stream
+        self._op_stream = stream
+        self._ev_op = torch.cuda.Event() if self.parts > 1 else None
         self._snap = None
-        self._streams = [stream]
-        if schedule == "staggered":
-            bounds = np.cumsum([0] + [len(x) for x in np.array_split(np.arange(self.C), self.parts)])
-            # sub-batch j: its child rows, child streams, flags and work buffer; part 0 runs
-            # on the island's stream, the others on streams of their own
-            self._part = [{"off": int(bounds[j]), "rows": slice(int(bounds[j]), int(bounds[j + 1])),
-                           "work": self.work if j == 0 else dp.ga_work(self.N)} for j in range(self.parts)]
-            for d in self._part:
-                r = d["rows"]
-                d.update(child={k: v[r] for k, v in self.child.items()}, rng=self.rng_child[r], flags=self.flags[r])
-            self._streams = [stream] + _side_streams(dev, stream, self.parts - 1)
-            self._ev_op = torch.cuda.Event()          # the last population operation (breed or replace)
-            self._pending = []                        # parts searched but not yet replaced, in breed order
-            self._last_replace = 0                    # part whose work buffer holds the last replace's source
         if stream is not None:
             stream.wait_stream(torch.cuda.current_stream(dev))     # the zero-filled buffers above
-        for st in self._streams[1:]:
-            st.wait_stream(torch.cuda.current_stream(dev) if stream is None else stream)
+        for st in streams[1:]:
+            st.wait_stream(stream)
         # the buffers were allocated on the creating stream and are used on the island's
         # own stream(s): tell the caching allocator, so a dropped island's blocks are not
         # handed out again while its kernels may still write them
-        self._side_streams = [st for st in self._streams if st is not None]
-        self._record_streams(self._owned())
-
-    def _owned(self):
-        ts = list(self.pop.values()) + list(self.child.values()) + [self.flags, self.rng_init, self.rng_child,
-                                                                    self.work]
-        if self.schedule == "staggered":
-            ts += [d["work"] for d in self._part[1:]]
-        return ts
+        self._own_streams = [st for st in streams if st is not None]
+        self._record_streams(list(self.pop.values()) + list(self.child.values())
+                             + [self.flags, self.rng_init, self.rng_child] + [p.work for p in self._parts])
 
     def _record_streams(self, tensors):
-        for st in self._side_streams:
+        for st in self._own_streams:
             for t in tensors:
                 t.record_stream(st)
 
@@ -261,49 +265,60 @@ class Island(Members):
         freed safely whatever the allocator knows)."""
         import torch
         self.flush()
-        for st in self._side_streams:
+        for st in self._own_streams:
             st.synchronize()
         torch.cuda.current_stream(self.pop["slot"].device).synchronize()
 
+    # Cross-stream ordering, all of it: _wait_op / _record_op chain the population
+    # operations, _fork / _join tie the chain to the caller's stream. Each does nothing
+    # when the stream it would order is the one the last operation ran on, which on a
+    # one-part island is every time (its only stream is the caller's).
+
+    def _wait_op(self, st):
+        """What `st` runs next comes after the last population operation."""
+        if st is not self._op_stream:
+            st.wait_event(self._ev_op)
+
+    def _record_op(self, st):
+        """A population operation (breed, replace, or the caller's writes taken
+        in by _fork) has just been enqueued on `st`."""
+        self._op_stream = st
+        if self._ev_op is not None:
+            self._ev_op.record(st)
+
     def _base(self):
         """The stream the caller orders its own work on: the island's stream as
-        given, else torch's current stream."""
+        given, else torch's current stream (part 0's own stream when that is
+        where the caller's work runs too: nothing to look up)."""
         import torch
-        return (self._user_stream if self._user_stream is not None
-                else torch.cuda.current_stream(self.pop["slot"].device))
+        return self.stream if self.stream is self._user_stream else torch.cuda.current_stream(self.pop["slot"].device)
 
     def _fork(self):
-        """Staggered: the population operations enqueued next come after the
-        caller's work enqueued so far on _base() (the chain's event takes it in)."""
-        s0 = self._streams[0]
+        """The population operations enqueued next come after the caller's work
+        enqueued so far on _base() (the chain takes it in on part 0's stream)."""
         b = self._base()
-        if b != s0:
-            s0.wait_stream(b)
-        s0.wait_event(self._ev_op)
-        self._ev_op.record(s0)
+        if b is not self.stream:
+            self.stream.wait_stream(b)
+        self._wait_op(self.stream)
+        self._record_op(self.stream)
 
     def _join(self):
-        """Staggered: the caller's stream (_base()) waits for the population's
-        last operation, so what it enqueues next sees the population as a batch
-        schedule on that stream would leave it (pending sub-batches aside)."""
-        self._base().wait_event(self._ev_op)
+        """The caller's stream (_base()) waits for the population's last
+        operation, so what it enqueues next sees the population as a one-part
+        island on that stream would leave it (pending sub-batches aside)."""
+        self._wait_op(self._base())
 
     def _on_stream(self, stream=None):
-        import contextlib
-
         import torch
         st = self.stream if stream is None else stream
-        return torch.cuda.stream(st) if st is not None else contextlib.nullcontext()
+        return torch.cuda.stream(st) if st is not None else _NO_STREAM
 
     def sync(self):
-        """Wait for the island's work: pending sub-batches are replaced first
-        (staggered schedule), then the island's stream is waited for."""
-        import torch
+        """Wait for the island's work: pending sub-batches are replaced first,
+        then the island's stream is waited for."""
         self.flush()
         if self.stream is not None:
             self.stream.synchronize()
-        elif self.schedule == "staggered":
-            torch.cuda.current_stream(self.pop["slot"].device).synchronize()
 
     def member(self, k: int) -> dict:
         self.sync()
@@ -326,31 +341,24 @@ class Island(Members):
 
     def initialize(self):
         """ga.cpp:429-434 for every member, then the population is sorted."""
-        if self.schedule == "staggered":
-            self._fork()
+        self._fork()
         with self._on_stream():
             p = self.pop
             self.dp.random_init(self.rng_init, p["slot"], p["room"])
             self.dp.local_search(p["slot"], p["room"], self.rng_init, self.max_steps, self.p1, self.p2, self.p3,
                                  out=(p["hcv"], p["scv"], p["feasible"], p["penalty"]))
             self.dp.ga_replace(p, None, self.work)
-            if self.schedule == "staggered":
-                self._ev_op.record()
-        if self.schedule == "staggered":
-            self._join()
+        self._record_op(self.stream)
+        self._join()
 
     def step(self):
         """One generation of C children (ga.cpp:543-585), enqueued on the island's
-        stream(s): the whole batch, or (staggered) each sub-batch in turn."""
-        if self.schedule == "staggered":
-            self._fork()
-            for j in range(self.parts):
-                self._part_step(j)
-            self._join()
-            self.generation += 1
-            return
-        with self._on_stream():
-            self._step()
+        stream(s): each sub-batch in turn."""
+        self._fork()
+        for j in range(self.parts):
+            self._advance(j)
+        self._join()
+        self.generation += 1
 
     def _search(self, c, rng, work):
         """LPT order (optional), localSearch and evaluation of children c (one
@@ -364,114 +372,93 @@ class Island(Members):
         self.dp.local_search(c["slot"], c["room"], rng, self.max_steps, self.p1, self.p2, self.p3, order=order,
                              out=(c["hcv"], c["scv"], c["feasible"], c["penalty"]))
 
-    def _step(self):
-        c = self.child
-        self.dp.ga_breed(self.pop["slot"], self.pop["room"], self.pop["penalty"], self.rng_child, c["slot"], c["room"],
-                         self.flags, self.p_cross, self.p_mut, self.skip)
-        self._search(c, self.rng_child, self.work)
-        self.dp.ga_replace(self.pop, c, self.work)
-        self.generation += 1
-
-    def _part_step(self, j: int):
+    def _advance(self, j: int):
         """Sub-batch j: bred from the population behind the last population
-        operation; then, with parts - 1 sub-batches pending, the oldest of them
-        is replaced behind that breed; then sub-batch j is searched."""
-        import torch
-        d, st = self._part[j], self._streams[j]
-        with self._on_stream(st):
-            torch.cuda.current_stream().wait_event(self._ev_op)           # breed(h) after replace(h - parts)
-            self.dp.ga_breed(self.pop["slot"], self.pop["room"], self.pop["penalty"], d["rng"], d["child"]["slot"],
-                             d["child"]["room"], d["flags"], self.p_cross, self.p_mut, self.skip)
-            self._ev_op.record()
-        if len(self._pending) >= self.parts - 1:
-            self._replace_oldest()                                          # replace(h - parts + 1) after breed(h)
-        with self._on_stream(st):
-            self._search(d["child"], d["rng"], d["work"])
-        self._pending.append(j)
+        operation; then, with parts - 1 older sub-batches pending, the oldest of
+        them is replaced behind that breed; then sub-batch j is searched (one
+        part: and replaced at once, the sub-batch parts - 1 behind being itself)."""
+        p = self._parts[j]
+        with self._on_stream(p.stream):
+            self._wait_op(p.stream)                                         # breed(h) after replace(h - parts)
+            self.dp.ga_breed(self.pop["slot"], self.pop["room"], self.pop["penalty"], p.rng, p.child["slot"],
+                             p.child["room"], p.flags, self.p_cross, self.p_mut, self.skip)
+            self._record_op(p.stream)
+            if self._pending and len(self._pending) >= self.parts - 1:
+                self._replace_oldest()                                      # replace(h - parts + 1) after breed(h)
+            self._search(p.child, p.rng, p.work)
+            self._pending.append(j)
+            if len(self._pending) >= self.parts:
+                self._replace_oldest()
 
     def _replace_oldest(self):
-        import torch
         j = self._pending.pop(0)
-        d = self._part[j]
-        with self._on_stream(self._streams[j]):
-            torch.cuda.current_stream().wait_event(self._ev_op)
-            self.dp.ga_replace(self.pop, d["child"], d["work"])
-            self._ev_op.record()
+        p = self._parts[j]
+        with self._on_stream(p.stream):
+            self._wait_op(p.stream)
+            self.dp.ga_replace(self.pop, p.child, p.work)
+            self._record_op(p.stream)
         self._last_replace = j
 
     def flush(self):
-        """Staggered schedule: replace the pending sub-batches in order, and make
-        the island's stream wait for the population's last operation (no-op for
-        the batch schedule)."""
-        import torch
-        if self.schedule != "staggered":
-            return
+        """Replace the pending sub-batches in order, and make the island's stream
+        wait for the population's last operation (one part: nothing is pending
+        and the last operation ran there)."""
         self._fork()
         while self._pending:
             self._replace_oldest()
         self._join()
-        with self._on_stream():
-            torch.cuda.current_stream().wait_event(self._ev_op)
-
-    def _work_of_last_replace(self):
-        return self._part[self._last_replace]["work"] if self.schedule == "staggered" else self.work
+        self._wait_op(self.stream)
 
     def snapshot(self) -> "Snapshot":
         """pop[0]'s (feasible, scv, hcv) and best_thread()'s source position,
         copied into pinned host memory behind the last replacement enqueued
-        (staggered: pending sub-batches stay pending, so the snapshot is the
-        population as the last replacement left it); Snapshot.values() waits for
-        that copy only, so the host can log generation g while generation g + 1
-        runs. Two pinned buffers and events are reused in turn (generation g's
-        snapshot is read after g + 1 has been enqueued)."""
+        (pending sub-batches stay pending, so the snapshot is the population as
+        the last replacement left it); Snapshot.values() waits for that copy
+        only, so the host can log generation g while generation g + 1 runs. Two
+        slots -- a pinned buffer, a device staging tensor and an event each --
+        are reused in turn (generation g's snapshot is read after g + 1 has
+        been enqueued). The staging tensor is the slot's own: consecutive
+        snapshots may run on different parts' streams with nothing ordering
+        them, and the later one must not write what the earlier one's copy to
+        the host still reads."""
         import torch
         if self._snap is None:
-            self._snap = [(torch.empty(4, dtype=torch.int32, pin_memory=True), torch.cuda.Event()) for _ in range(2)]
-            self._snap_meta = torch.empty(4, dtype=torch.int32, device=self.pop["slot"].device)
-            self._record_streams([self._snap_meta])
+            dev = self.pop["slot"].device
+            self._snap = [(torch.empty(4, dtype=torch.int32, pin_memory=True),
+                           torch.empty(4, dtype=torch.int32, device=dev), torch.cuda.Event()) for _ in range(2)]
+            self._record_streams([m for _, m, _ in self._snap])
             self._snap_i = 0
             self._snap_owner = [None, None]
         i = self._snap_i
-        host, ev = self._snap[i]
+        host, m, ev = self._snap[i]
         if self._snap_owner[i] is not None:
-            self._snap_owner[i].values()     # the buffer's previous snapshot, read before the reuse
+            self._snap_owner[i].values()     # the slot's previous snapshot, read before the reuse
         self._snap_i ^= 1
-        st = self._streams[self._last_replace] if self.schedule == "staggered" else None
-        with self._on_stream(st):
+        last = self._parts[self._last_replace]
+        with self._on_stream(last.stream):
             off = int(self.dp.lib.tt_ga_work_source_offset(self.N, self.dp.E))
-            p, w = self.pop, self._work_of_last_replace()
-            m = self._snap_meta
+            p = self.pop
             m[0] = p["feasible"][0]
             m[1] = p["scv"][0]
             m[2] = p["hcv"][0]
-            m[3] = w[off:off + 4].view(torch.int32)[0]
+            m[3] = last.work[off:off + 4].view(torch.int32)[0]
             host.copy_(m, non_blocking=True)
             ev.record()
-        snap = Snapshot(host, ev, self.generation, self.N - self._last_batch(), self.N, self._thread_base())
+        snap = Snapshot(host, ev, self.generation, self.N - last.n, self.N, last.off)
         self._snap_owner[i] = snap
         return snap
-
-    def _last_batch(self) -> int:
-        """Children merged by the last replacement (best_thread's offset)."""
-        if self.schedule != "staggered":
-            return self.C
-        return self._part[self._last_replace]["child"]["slot"].shape[0]
-
-    def _thread_base(self) -> int:
-        """Child slot of the last replacement's first child (staggered: its part's offset)."""
-        return self._part[self._last_replace]["off"] if self.schedule == "staggered" else 0
 
     def best_thread(self) -> int:
         """The reference thread (ga.cpp:498, one per child slot) whose
         replacement put the current pop[0] in place: child c of the last
         tt_ga_replace (the source position it leaves in its own slot of the
-        work buffer, tt_ga_work_source_offset), else thread 0. Staggered: the
-        child slot index over all sub-batches, after the pending ones are
-        replaced."""
+        work buffer, tt_ga_work_source_offset), else thread 0: the child slot
+        index over all sub-batches, after the pending ones are replaced."""
         self.sync()
-        src = self.dp.ga_work_source(self._work_of_last_replace(), self.N)
-        k = self.N - self._last_batch()
-        return self._thread_base() + src - k if self.generation > 0 and k <= src < self.N else 0
+        last = self._parts[self._last_replace]
+        src = self.dp.ga_work_source(last.work, self.N)
+        k = self.N - last.n
+        return last.off + src - k if self.generation > 0 and k <= src < self.N else 0
 
 
 class Snapshot:
