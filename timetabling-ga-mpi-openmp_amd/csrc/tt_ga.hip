@@ -14,6 +14,7 @@
 
 #include "tt_internal.h"
 #include "tt_match.h"
+#include "tt_replace_internal.h"
 
 namespace ttga {
 
@@ -94,12 +95,7 @@ static uint32_t host_pm_pow(long n) {
 }
 
 // ---------------------------------------------------------------- replace + sort
-// (penalty, position) as one u64; penalties compare as unsigned, so the -1 of an
-// invalid genome (tt_eval's sentinel; valid penalties are >= 0) sorts last
-__device__ __forceinline__ uint64_t sort_key(int32_t penalty, int pos) {
-    return ((uint64_t)(uint32_t)penalty << 32) | (uint32_t)pos;
-}
-
+// keys are sort_key(penalty, position) (tt_replace_internal.h): penalties compare as unsigned
 // keys of the merged population: positions < N-C from pop, the rest from the children
 __global__ void replace_keys_kernel(const int32_t* __restrict__ pen, const int32_t* __restrict__ cpen, int N, int C,
                                     int NP, uint64_t* __restrict__ keys) {
@@ -135,7 +131,6 @@ __global__ __launch_bounds__(1024) void bitonic_lds_kernel(uint64_t* __restrict_
 // tile, the stages k <= kSortTile completely (full) or, for a stage k above the
 // tile, its steps j < kSortTile (after the global steps j >= kSortTile). The
 // direction of a pair is (i & k) of its global index i, as in one global pass.
-constexpr int kSortTile = 8192;
 __global__ __launch_bounds__(1024) void bitonic_tile_kernel(uint64_t* __restrict__ keys, int k_stage) {
     __shared__ uint64_t sk[kSortTile];
     const long base = (long)blockIdx.x * kSortTile;
@@ -183,7 +178,6 @@ __global__ void bitonic_step_kernel(uint64_t* __restrict__ keys, int NP, int k, 
 // kPrepBlocks workgroups: flag[g] = 1 when workgroup g's share of the survivors
 // is in key order (all of them together: the survivors are); ckeys = the
 // children's keys (padded to CP), sorted by the next launch
-constexpr int kPrepBlocks = 64;
 __global__ __launch_bounds__(256) void replace_prep_kernel(const int32_t* __restrict__ pen,
                                                            const int32_t* __restrict__ cpen, int N, int C, int CP,
                                                            uint64_t* __restrict__ ckeys, int32_t* __restrict__ flag) {
@@ -194,10 +188,6 @@ __global__ __launch_bounds__(256) void replace_prep_kernel(const int32_t* __rest
     for (int i = gt; i + 1 < k; i += nth) ok &= (uint32_t)pen[i] <= (uint32_t)pen[i + 1];
     ok = __syncthreads_and(ok);
     if (threadIdx.x == 0) flag[blockIdx.x] = ok ? 1 : 0;
-}
-// every workgroup's flag set (call with blockDim >= kPrepBlocks, every thread)
-__device__ __forceinline__ bool survivors_sorted(const int32_t* flag) {
-    return __syncthreads_and(threadIdx.x < kPrepBlocks ? flag[threadIdx.x] != 0 : true);
 }
 
 // merge path: output i takes the i-th smallest of survivors (pen[a], a) and ckeys
@@ -229,16 +219,7 @@ __global__ __launch_bounds__(1024) void replace_fallback_sort_kernel(const int32
         keys[i] = i >= N ? ~0ull : sort_key(i < N - C ? pen[i] : cpen[i - (N - C)], i);
     __threadfence_block();
     __syncthreads();
-    for (int k = 2; k <= NP; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int q = threadIdx.x; q < NP / 2; q += blockDim.x) {
-                const int i = ((q & ~(j - 1)) << 1) | (q & (j - 1)), l = i + j;
-                const uint64_t x = keys[i], y = keys[l];
-                if ((x > y) == ((i & k) == 0)) { keys[i] = y; keys[l] = x; }
-            }
-            __threadfence_block();
-            __syncthreads();
-        }
+    bitonic_global(keys, NP);
     for (int i = threadIdx.x; i < N; i += blockDim.x) mkeys[i] = keys[i];
 }
 
@@ -320,7 +301,6 @@ __global__ __launch_bounds__(1024) void sort_reg_kernel(uint64_t* __restrict__ k
 // one lane per (key, tile), a binary search each, summed over the key's lanes.
 // Two launches spread over NP/kRankTile and NP*NT/256 workgroups instead of one
 // workgroup doing all 91 bitonic steps (64 us at 8,192 keys on one CU).
-constexpr int kRankTile = 256;
 
 // rank of keys[i] among keys[0..NP) (tiles of kRankTile sorted); every thread of
 // the group of NT lanes (NT = NP / kRankTile, a power of two <= 64) of key i calls it
@@ -355,27 +335,6 @@ __global__ __launch_bounds__(256) void rank_scatter_kernel(const uint64_t* __res
     uint64_t x;
     const int r = tile_rank(keys, i, NT, b, x);
     if (b == 0) out[r] = x;
-}
-
-// copy two rows of E bytes (slot and room), 512 bytes per lane block with all
-// loads in flight before the stores
-__device__ __forceinline__ void copy_rows2(uint8_t* __restrict__ d0, const uint8_t* __restrict__ s0,
-                                           uint8_t* __restrict__ d1, const uint8_t* __restrict__ s1, int E,
-                                           int lane) {
-    for (int e0 = 0; e0 < E; e0 += 512) {
-        uint8_t a[8], b[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int e = e0 + 64 * k + lane;
-            a[k] = e < E ? s0[e] : 0;
-            b[k] = e < E ? s1[e] : 0;
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int e = e0 + 64 * k + lane;
-            if (e < E) { d0[e] = a[k]; d1[e] = b[k]; }
-        }
-    }
 }
 
 // gather the sorted population into the work rows (one wave per row)
@@ -448,20 +407,8 @@ __global__ __launch_bounds__(256) void lpt_rank_order_kernel(const uint64_t* __r
     if (b == 0 && r < n) order[r] = (int32_t)(uint32_t)x;
 }
 
-static int pow2_at_least(int n) {
-    int p = 1;
-    while (p < n) p <<= 1;
-    return p;
-}
-
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-}  // namespace ttga
-
-using namespace ttga;
-
 // ascending bitonic sort of NP (a power of two) u64 keys on stream st
-static void sort_keys(uint64_t* keys, int NP, hipStream_t st) {
+void sort_keys(uint64_t* keys, int NP, hipStream_t st) {
     if (NP >= 8 && NP <= kSortTile) {
         hipLaunchKernelGGL(sort_reg_kernel<8>, dim3(1), dim3(std::max(64, NP / 8)), 0, st, keys, NP);
         return;
@@ -481,13 +428,25 @@ static void sort_keys(uint64_t* keys, int NP, hipStream_t st) {
     }
 }
 
+// NP keys in [2*kRankTile, kSortTile]: sorted by tiles + ranks
+bool use_rank_sort(int NP) { return NP >= 2 * kRankTile && NP <= kSortTile; }
+// the tiles of the rank sort (ranks are then counted by the caller's kernel)
+void sort_rank_tiles(uint64_t* keys, int NP, hipStream_t st) {
+    hipLaunchKernelGGL(sort_reg_kernel<4>, dim3(NP / kRankTile), dim3(kRankTile / 4), 0, st, keys, kRankTile);
+}
+void rank_scatter(const uint64_t* keys, int NP, uint64_t* out, hipStream_t st) {
+    const int NT = NP / kRankTile;
+    hipLaunchKernelGGL(rank_scatter_kernel, dim3(NP * NT / 256), dim3(256), 0, st, keys, NP, NT, out);
+}
+
 // launched from tt_rooms.hip (masked variants of the matcher and of mutation)
-namespace ttga {
 int launch_assign_masked(const tt_problem* p, const uint8_t* slot, uint8_t* room, int P, const uint8_t* mask,
                          uint8_t bit, hipStream_t st);
 int launch_mutation_masked(const tt_problem* p, uint8_t* slot, uint8_t* room, int64_t* rng, int P,
                            const uint8_t* mask, uint8_t bit, hipStream_t st);
 }  // namespace ttga
+
+using namespace ttga;
 
 extern "C" int tt_ga_breed(const tt_problem* p, const uint8_t* pop_slot, const uint8_t* pop_room,
                            const int32_t* pop_penalty, int N, int64_t* rng, int C, double p_cross, double p_mut,
@@ -510,13 +469,6 @@ extern "C" int tt_ga_breed(const tt_problem* p, const uint8_t* pop_slot, const u
     return launch_mutation_masked(p, child_slot, child_room, rng, C, child_flags, kFlagMutate, st);
 }
 
-// NP keys in [2*kRankTile, kSortTile]: sorted by tiles + ranks
-static bool use_rank_sort(int NP) { return NP >= 2 * kRankTile && NP <= kSortTile; }
-// the tiles of the rank sort (ranks are then counted by the caller's kernel)
-static void sort_rank_tiles(uint64_t* keys, int NP, hipStream_t st) {
-    hipLaunchKernelGGL(sort_reg_kernel<4>, dim3(NP / kRankTile), dim3(kRankTile / 4), 0, st, keys, kRankTile);
-}
-
 // work layout: sort keys [pow2(N)] u64 | slot rows [N][E] | room rows [N][E] |
 // meta [N][4] i32 | the source slot (256 B, written only by tt_ga_replace) |
 // merged keys [N] u64 | child keys [kSortTile] u64 | merge flag (256 B) |
@@ -526,6 +478,25 @@ static size_t work_source_offset(int N, int E) {
     return align256(8 * NP) + 2 * align256((size_t)N * E) + align256(16 * (size_t)N);
 }
 static size_t work_merge_offset(int N, int E) { return work_source_offset(N, E) + 256; }
+
+namespace ttga {
+GaWork ga_work_layout(void* work, int N, int E) {
+    uint8_t* w = (uint8_t*)work;
+    GaWork g;
+    g.keys = (uint64_t*)w;
+    g.ws = w + align256(8 * (size_t)pow2_at_least(N));
+    g.wr = g.ws + align256((size_t)N * E);
+    g.wm = (int32_t*)(g.wr + align256((size_t)N * E));
+    g.source = (int32_t*)(w + work_source_offset(N, E));
+    g.mkeys = (uint64_t*)(w + work_merge_offset(N, E));
+    return g;
+}
+
+void replace_scatter(int E, int N, const GaWork& w, uint8_t* ps, uint8_t* pr, int32_t* ph, int32_t* psc, uint8_t* pf,
+                     int32_t* pp, hipStream_t st) {
+    hipLaunchKernelGGL(replace_scatter_kernel, dim3(N), dim3(64), 0, st, E, w.ws, w.wr, w.wm, ps, pr, ph, psc, pf, pp);
+}
+}  // namespace ttga
 
 extern "C" size_t tt_ga_work_bytes(int N, int E) {
     if (N < 1 || E < 1) return 0;
@@ -552,18 +523,15 @@ extern "C" int tt_ga_replace(const tt_problem* p, uint8_t* pop_slot, uint8_t* po
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int E = p->E, NP = pow2_at_least(N);
-    uint8_t* w = (uint8_t*)work;
-    uint64_t* keys = (uint64_t*)w;
-    uint8_t* ws = w + align256(8 * (size_t)NP);
-    uint8_t* wr = ws + align256((size_t)N * E);
-    int32_t* wm = (int32_t*)(wr + align256((size_t)N * E));
+    const GaWork gw = ga_work_layout(work, N, E);
+    uint64_t* keys = gw.keys;
     const uint64_t* sorted = keys;
     // C = 0 sorts a population with no order to rely on (the initial sort,
     // ga.cpp:433-434): the multi-workgroup sort, not the merge path's
     // one-workgroup fallback (which a generation meets only when a migrant
     // survives out of order, C = 1)
     if (C > 0 && C <= kSortTile) {
-        uint64_t* mkeys = (uint64_t*)(w + work_merge_offset(N, E));
+        uint64_t* mkeys = gw.mkeys;
         uint64_t* ckeys = (uint64_t*)((uint8_t*)mkeys + align256(8 * (size_t)N));
         int32_t* flag = (int32_t*)(ckeys + kSortTile);
         const int CP = pow2_at_least(std::max(C, 2));
@@ -572,9 +540,8 @@ extern "C" int tt_ga_replace(const tt_problem* p, uint8_t* pop_slot, uint8_t* po
         const uint64_t* csorted = ckeys;
         if (use_rank_sort(CP)) {
             uint64_t* cs2 = (uint64_t*)((uint8_t*)flag + 256);
-            const int NT = CP / kRankTile;
             sort_rank_tiles(ckeys, CP, st);
-            hipLaunchKernelGGL(rank_scatter_kernel, dim3(CP * NT / 256), dim3(256), 0, st, ckeys, CP, NT, cs2);
+            rank_scatter(ckeys, CP, cs2, st);
             csorted = cs2;
         } else {
             sort_keys(ckeys, CP, st);
@@ -591,9 +558,8 @@ extern "C" int tt_ga_replace(const tt_problem* p, uint8_t* pop_slot, uint8_t* po
     }
     hipLaunchKernelGGL(replace_gather_kernel, dim3(N), dim3(64), 0, st, E, N, C, sorted, pop_slot, pop_room, pop_hcv,
                        pop_scv, pop_feasible, pop_penalty, child_slot, child_room, child_hcv, child_scv, child_feasible,
-                       child_penalty, ws, wr, wm, (int32_t*)(w + work_source_offset(N, E)));
-    hipLaunchKernelGGL(replace_scatter_kernel, dim3(N), dim3(64), 0, st, E, ws, wr, wm, pop_slot, pop_room, pop_hcv,
-                       pop_scv, pop_feasible, pop_penalty);
+                       child_penalty, gw.ws, gw.wr, gw.wm, gw.source);
+    replace_scatter(E, N, gw, pop_slot, pop_room, pop_hcv, pop_scv, pop_feasible, pop_penalty, st);
     return check_hip(hipGetLastError(), "tt_ga_replace launch");
 }
 

@@ -11,7 +11,14 @@
 //
 //   ttga-ga -i instance.tim [-s seed] [-p type] [-c children]
 //           [-p1 x -p2 y -p3 z] [--gpus G] [--islands K] [--pop N] [--generations n] [--rccl] [--stagger]
-//           [--report]
+//           [--report] [--unique]
+//
+// --unique: duplicate-free replacement (include/ttga_unique.h): a child whose
+// genome is already in the population, or in an earlier child of its sub-batch,
+// is dropped on the device. After the solution lines and before any report
+// line, one `unique` line per island: children bred, children dropped, distinct
+// genomes left (the same line as python -m ttga.islands --unique prints).
+// Migration is unchanged: a migrant may duplicate a member of its destination.
 //
 // --report: after the solution lines, one `report` line per island: the best
 // member's six constraint parts, their sums over the population and its slot
@@ -62,6 +69,7 @@
 #include <vector>
 
 #include "../../include/ttga_report.h"
+#include "../../include/ttga_unique.h"
 
 namespace {
 
@@ -94,6 +102,7 @@ struct Control {
     bool rccl = false;
     int stagger = 0;                              // sub-batches of the staggered schedule (0: batch)
     bool report = false;                          // a population report line per island
+    bool unique = false;                          // duplicate-free replacement, a unique line per island
 };
 
 // Control::Control (Control.cpp:3-137) plus the --gpus/--pop/--generations extensions.
@@ -110,6 +119,10 @@ Control parse_control(int argc, char** argv) {
     }
     if (auto it = std::find(args.begin(), args.end(), "--report"); it != args.end()) {
         c.report = true;
+        args.erase(it);
+    }
+    if (auto it = std::find(args.begin(), args.end(), "--unique"); it != args.end()) {
+        c.unique = true;
         args.erase(it);
     }
     for (const char* k : {"--gpus", "--islands", "--pop", "--generations", "--children", "--stagger-parts"}) {
@@ -407,6 +420,17 @@ Json report_line(const std::vector<int32_t>& parts, const std::vector<int32_t>& 
     return wrap("report", rep);
 }
 
+// --unique (ttga/ga.py unique_line)
+Json unique_line(long children, long dropped, long distinct, int proc, int island) {
+    Json u;
+    u.obj["children"] = Json::I(children);
+    u.obj["dropped"] = Json::I(dropped);
+    u.obj["distinct"] = Json::I(distinct);
+    u.obj["procID"] = Json::I(proc);
+    u.obj["island"] = Json::I(island);
+    return wrap("unique", u);
+}
+
 // ---------------------------------------------------------------- islands
 struct Pop {
     int n = 0, E = 0;
@@ -467,7 +491,7 @@ struct Island {
     // on stream s with its own work buffer; every population operation (breed or replace)
     // follows the previous one, so sub-batch h is bred after the replacement of h - parts
     // and h - parts + 1 is replaced after the breed of h. parts == 1 (no --stagger) is the
-    // batch schedule: part[0] = {0, C, st, work}, each sub-batch replaced behind its own
+    // batch schedule: part[0] = {0, C, st, its work buffer}, each sub-batch replaced behind its own
     // search, and neither ev_op nor another stream or work buffer exists
     int parts = 1;
     struct Part { int off = 0, n = 0; hipStream_t s = nullptr; void* work = nullptr; };
@@ -476,8 +500,19 @@ struct Island {
     hipStream_t op_stream = nullptr;                  // the stream that operation ran on
     std::vector<int> pending;                         // parts searched, not yet replaced (breed order)
     int last_replace = 0;
+    // --unique: every replacement is tt_ga_replace_unique; replacement number r leaves its
+    // kept count in kept_log[r] on the device (the initial sort, C = 0, has none), read once
+    // at the end, so no generation waits for it; children = those that went through a replacement
+    bool unique = false;
+    uint8_t* keep = nullptr;                          // [C], part j's flags at keep + off
+    int32_t* kept_log = nullptr;
+    long kept_cap = 0, kept_used = 0, children = 0;
 
-    void setup(const Instance& inst) {
+    size_t work_bytes(int n) const {
+        return std::max<size_t>(unique ? tt_ga_unique_work_bytes(N, n, E) : tt_ga_work_bytes(N, E), 16);
+    }
+
+    void setup(const Instance& inst, long replacements) {
         check_hip(hipSetDevice(device), "hipSetDevice");
         check_tt(tt_problem_create(inst.E, inst.R, inst.F, inst.S, inst.room_size.data(), inst.student_events.data(),
                                    inst.room_features.data(), inst.event_features.data(), device, &tp),
@@ -494,7 +529,12 @@ struct Island {
         check_hip(hipMemcpy(rng_child, s.data() + N, 8 * (size_t)C, hipMemcpyHostToDevice), "hipMemcpy");
         check_hip(hipMalloc(&flags, (size_t)C), "hipMalloc");
         if (C >= kLptMinChildren) check_hip(hipMalloc(&order, 4 * (size_t)C), "hipMalloc");
-        check_hip(hipMalloc(&work, std::max<size_t>(tt_ga_work_bytes(N, E), 16)), "hipMalloc");
+        if (unique) {
+            kept_cap = std::max(replacements, 1L);
+            check_hip(hipMalloc(&keep, (size_t)C), "hipMalloc");
+            check_hip(hipMalloc(&kept_log, 4 * (size_t)kept_cap), "hipMalloc");
+            check_hip(hipMemset(kept_log, 0, 4 * (size_t)kept_cap), "hipMemset");
+        }
         migrant_bytes = 2 * (size_t)E + 13;
         check_hip(hipMalloc(&send_best, migrant_bytes), "hipMalloc");
         check_hip(hipMalloc(&send_second, migrant_bytes), "hipMalloc");
@@ -506,11 +546,10 @@ struct Island {
             part[j].off = off;
             part[j].n = C / parts + (j < C % parts ? 1 : 0);
             off += part[j].n;
-            if (j > 0) {
-                check_hip(hipStreamCreateWithFlags(&part[j].s, hipStreamNonBlocking), "hipStreamCreate");
-                check_hip(hipMalloc(&part[j].work, std::max<size_t>(tt_ga_work_bytes(N, E), 16)), "hipMalloc");
-            }
+            if (j > 0) check_hip(hipStreamCreateWithFlags(&part[j].s, hipStreamNonBlocking), "hipStreamCreate");
+            check_hip(hipMalloc(&part[j].work, work_bytes(part[j].n)), "hipMalloc");
         }
+        work = part[0].work;
     }
 
     // All cross-stream ordering: what s runs next comes after the last population
@@ -536,9 +575,15 @@ struct Island {
         check_tt(tt_local_search_eval(tp, pop.slot, pop.room, rng_init, N, max_steps, p1, p2, p3, nullptr, pop.hcv,
                                       pop.scv, pop.feasible, pop.penalty, st),
                  "tt_local_search_eval");
-        check_tt(tt_ga_replace(tp, pop.slot, pop.room, pop.hcv, pop.scv, pop.feasible, pop.penalty, N, pop.slot,
-                               pop.room, pop.hcv, pop.scv, pop.feasible, pop.penalty, 0, work, st),
-                 "tt_ga_replace");
+        if (unique)
+            check_tt(tt_ga_replace_unique(tp, pop.slot, pop.room, pop.hcv, pop.scv, pop.feasible, pop.penalty, N,
+                                          pop.slot, pop.room, pop.hcv, pop.scv, pop.feasible, pop.penalty, 0, nullptr,
+                                          nullptr, 0, work, st),
+                     "tt_ga_replace_unique");
+        else
+            check_tt(tt_ga_replace(tp, pop.slot, pop.room, pop.hcv, pop.scv, pop.feasible, pop.penalty, N, pop.slot,
+                                   pop.room, pop.hcv, pop.scv, pop.feasible, pop.penalty, 0, work, st),
+                     "tt_ga_replace");
         wrote_population(st);
     }
 
@@ -579,9 +624,40 @@ struct Island {
 
     void replace(int off, int n, hipStream_t s, void* w) {
         Pop c = child_rows(off, n);
+        if (unique) {
+            if (kept_used >= kept_cap) die("more replacements than planned for");
+            check_tt(tt_ga_replace_unique(tp, pop.slot, pop.room, pop.hcv, pop.scv, pop.feasible, pop.penalty, N, c.slot,
+                                          c.room, c.hcv, c.scv, c.feasible, c.penalty, n, keep + off,
+                                          kept_log + kept_used++, 0, w, s),
+                     "tt_ga_replace_unique");
+            children += n;
+            return;
+        }
         check_tt(tt_ga_replace(tp, pop.slot, pop.room, pop.hcv, pop.scv, pop.feasible, pop.penalty, N, c.slot, c.room,
                                c.hcv, c.scv, c.feasible, c.penalty, n, w, s),
                  "tt_ga_replace");
+    }
+
+    // the --unique line of the population with every sub-batch replaced: the kept counts
+    // of all replacements in one copy, and the first occurrences of the genomes
+    Json unique_report(int proc, int island) {
+        flush();
+        std::vector<int32_t> kept(kept_used), first(N);
+        int32_t* d_first = nullptr;
+        void* d_work = nullptr;
+        check_hip(hipMalloc(&d_first, 4 * (size_t)N), "hipMalloc");
+        check_hip(hipMalloc(&d_work, std::max<size_t>(tt_genome_work_bytes(N, E), 16)), "hipMalloc");
+        check_tt(tt_genome_first(tp, pop.slot, pop.room, N, d_first, 0, d_work, st), "tt_genome_first");
+        check_hip(hipMemcpyAsync(first.data(), d_first, 4 * (size_t)N, hipMemcpyDeviceToHost, st), "hipMemcpy");
+        if (!kept.empty())
+            check_hip(hipMemcpyAsync(kept.data(), kept_log, 4 * kept.size(), hipMemcpyDeviceToHost, st), "hipMemcpy");
+        check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
+        (void)hipFree(d_first);
+        (void)hipFree(d_work);
+        long kept_sum = 0, distinct = 0;
+        for (size_t r = 0; r < kept.size(); r++) kept_sum += kept[r];
+        for (int i = 0; i < N; i++) distinct += first[i] == i;
+        return unique_line(children, children - kept_sum, distinct, proc, island);
     }
 
     // one generation of C children (ga.cpp:543-585): each sub-batch in turn
@@ -651,8 +727,9 @@ struct Island {
                                  hipMemcpyDeviceToHost, p.s),
                   "hipMemcpy");
         check_hip(hipStreamSynchronize(p.s), "hipStreamSynchronize");
-        const long k = N - p.n;
-        return src >= k && src < N ? (int)(p.off + src - k) : 0;
+        // the child's source word: N - n + c from tt_ga_replace, N + c from tt_ga_replace_unique
+        const long k = unique ? N : N - p.n, end = unique ? N + p.n : N;
+        return src >= k && src < end ? (int)(p.off + src - k) : 0;
     }
 
     // setCurrentCost (ga.cpp:203-228) on pop[0] as the last replacement left it
@@ -709,12 +786,12 @@ struct Island {
     void release() {
         pop.release();
         child.release();
-        for (void* p : {(void*)rng_init, (void*)rng_child, (void*)flags, work, (void*)order, (void*)send_best,
-                        (void*)send_second, (void*)recv_buf})
+        for (void* p : {(void*)rng_init, (void*)rng_child, (void*)flags, (void*)order, (void*)send_best,
+                        (void*)send_second, (void*)recv_buf, (void*)keep, (void*)kept_log})
             if (p) (void)hipFree(p);
-        for (size_t j = 1; j < part.size(); j++) {
+        for (size_t j = 0; j < part.size(); j++) {
             if (part[j].work) (void)hipFree(part[j].work);
-            if (part[j].s) (void)hipStreamDestroy(part[j].s);
+            if (j > 0 && part[j].s) (void)hipStreamDestroy(part[j].s);
         }
         if (ev_op) (void)hipEventDestroy(ev_op);
         if (st) (void)hipStreamDestroy(st);
@@ -768,6 +845,7 @@ int main(int argc, char** argv) {
         I.seed = island_seed(ctl.seed, k);
         I.p1 = ctl.p1; I.p2 = ctl.p2; I.p3 = ctl.p3;
         I.parts = ctl.stagger >= 2 ? std::min(ctl.stagger, C) : 1;
+        I.unique = ctl.unique;
     }
     std::vector<ncclComm_t> comms(K, nullptr);
     if (rccl) {
@@ -783,7 +861,7 @@ int main(int argc, char** argv) {
     auto sync = [](Island& I) { check_hip(hipStreamSynchronize(I.st), "hipStreamSynchronize"); };
     auto run = [&](int k) {
         Island& I = isl[k];
-        I.setup(inst);
+        I.setup(inst, (long)gens * I.parts);
         if (k == 0) I.initialize();
         sync(I);
         barrier.wait();
@@ -889,6 +967,11 @@ int main(int argc, char** argv) {
         check_hip(hipMemcpy(rm.data(), I.pop.room, I.E, hipMemcpyDeviceToHost), "hipMemcpy");
         out.line(solution_line(b.feasible, b.scv, b.hcv, sl, rm, k, seconds_since(t_begin)));
     }
+    if (ctl.unique)
+        for (int k = 0; k < K; k++) {
+            check_hip(hipSetDevice(isl[k].device), "hipSetDevice");
+            out.line(isl[k].unique_report(k, k));
+        }
     if (ctl.report)
         for (int k = 0; k < K; k++) {
             check_hip(hipSetDevice(isl[k].device), "hipSetDevice");

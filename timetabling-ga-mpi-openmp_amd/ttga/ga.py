@@ -11,6 +11,11 @@ kernels (include/ttga.h):
   members, re-sorting by penalty (tt_ga_replace). C = 1 is the reference's
   single-thread steady state; C > 1 is the batched counterpart of its
   OpenMP threads (every thread breeding against the shared population);
+* optionally (Island(unique=True)) a child whose genome is already in the
+  population, or in an earlier child of its sub-batch, is dropped instead of
+  replacing a member (tt_ga_replace_unique): an addition, ga.cpp has no
+  such test. Migration is unchanged: a migrant may duplicate a member of its
+  destination;
 * migration (ga.cpp:514-540) and the final MIN reduction (ga.cpp:234-257) are
   in ttga.islands.
 
@@ -183,12 +188,20 @@ class Island(Members):
     torch's current stream) and make that stream wait for the last of them, so
     the caller's next reads and writes of the population are ordered as on a
     one-part island.
+
+    unique=True: every replacement is tt_ga_replace_unique (include/ttga_unique.h):
+    a child whose genome (slot row + room row) equals a member's or an earlier
+    child's of the same sub-batch is dropped, decided on the device with no
+    host synchronisation; the D kept children replace the D worst members. A
+    population whose genomes are pairwise distinct stays so, migrants aside:
+    migration is unchanged and a migrant may duplicate a member of its
+    destination. unique_stats() reports the children bred and dropped.
     """
 
     def __init__(self, dp, pop_size: int = 10, children: int = 1, max_steps: int = 200, seed: int = 1,
                  p_cross: float = 0.8, p_mut: float = 0.5, skip_init_draws: bool = True, device=None,
                  p1: float = 1.0, p2: float = 1.0, p3: float = 0.0, lpt: bool | None = None, stream=None,
-                 schedule: str = "batch", parts: int = 2):
+                 schedule: str = "batch", parts: int = 2, unique: bool = False):
         """stream: a torch.cuda.Stream of the island's own, or None (torch's current
         stream). Islands multiplexed on one GPU (ttga.islands --islands K) each take
         one, so one island's launches fill the SIMD slots another's local-search tail
@@ -215,7 +228,7 @@ class Island(Members):
         self.flags = torch.zeros(self.C, dtype=torch.uint8, device=dev)
         self.rng_init = torch.from_numpy(stream_seeds(seed, 0, self.N)).to(dev)
         self.rng_child = torch.from_numpy(stream_seeds(seed, self.N, self.C)).to(dev)
-        self.work = dp.ga_work(self.N)
+        self.unique = bool(unique)
         self.generation = 0
         self.schedule = schedule
         self.parts = int(parts) if schedule == "staggered" else 1
@@ -234,9 +247,24 @@ class Island(Members):
         self._parts = []
         for j, st in enumerate(streams):
             r = slice(bounds[j], bounds[j + 1])
+            n = r.stop - r.start
             self._parts.append(types.SimpleNamespace(
-                off=r.start, n=r.stop - r.start, child={k: v[r] for k, v in self.child.items()}, rng=self.rng_child[r],
-                flags=self.flags[r], work=self.work if j == 0 else dp.ga_work(self.N), stream=st))
+                off=r.start, n=n, child={k: v[r] for k, v in self.child.items()}, rng=self.rng_child[r],
+                flags=self.flags[r], work=dp.ga_unique_work(self.N, n) if self.unique else dp.ga_work(self.N),
+                stream=st))
+        self.work = self._parts[0].work
+        # unique: each part's keep flags and kept count, the children dropped so far (added up
+        # on the replacing stream) and, on the host, the children that went through a replacement
+        self._extra = []
+        if self.unique:
+            for p in self._parts:
+                p.keep = torch.zeros(p.n, dtype=torch.uint8, device=dev)
+                p.n_kept = torch.zeros(1, dtype=torch.int32, device=dev)
+                self._extra += [p.keep, p.n_kept]
+            self._init_kept = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._dropped = torch.zeros(1, dtype=torch.int64, device=dev)
+            self._extra += [self._init_kept, self._dropped]
+        self._replaced = 0
         self._pending = []                            # parts searched but not yet replaced, in breed order
         self._last_replace = 0                        # part whose work buffer holds the last replace's source
         # the last population operation (breed or replace): the stream it ran on, and (several
@@ -253,7 +281,8 @@ class Island(Members):
         # handed out again while its kernels may still write them
         self._own_streams = [st for st in streams if st is not None]
         self._record_streams(list(self.pop.values()) + list(self.child.values())
-                             + [self.flags, self.rng_init, self.rng_child] + [p.work for p in self._parts])
+                             + [self.flags, self.rng_init, self.rng_child] + [p.work for p in self._parts]
+                             + self._extra)
 
     def _record_streams(self, tensors):
         for st in self._own_streams:
@@ -347,7 +376,10 @@ class Island(Members):
             self.dp.random_init(self.rng_init, p["slot"], p["room"])
             self.dp.local_search(p["slot"], p["room"], self.rng_init, self.max_steps, self.p1, self.p2, self.p3,
                                  out=(p["hcv"], p["scv"], p["feasible"], p["penalty"]))
-            self.dp.ga_replace(p, None, self.work)
+            if self.unique:
+                self.dp.ga_replace_unique(p, None, self.work, n_kept=self._init_kept)
+            else:
+                self.dp.ga_replace(p, None, self.work)
         self._record_op(self.stream)
         self._join()
 
@@ -395,9 +427,36 @@ class Island(Members):
         p = self._parts[j]
         with self._on_stream(p.stream):
             self._wait_op(p.stream)
-            self.dp.ga_replace(self.pop, p.child, p.work)
+            if self.unique:
+                self.dp.ga_replace_unique(self.pop, p.child, p.work, p.keep, p.n_kept)
+                self._dropped += p.n - p.n_kept               # on the device, behind the replacement
+                self._replaced += p.n
+            else:
+                self.dp.ga_replace(self.pop, p.child, p.work)
             self._record_op(p.stream)
         self._last_replace = j
+
+    def _source_range(self, part):
+        """(k, n): the source word of the part's last replacement names its child
+        c when k <= word < n, as word - k (tt_ga_replace: positions N - C + c;
+        tt_ga_replace_unique: N + c)."""
+        return (self.N, self.N + part.n) if self.unique else (self.N - part.n, self.N)
+
+    def unique_stats(self) -> dict:
+        """Island(unique=True): the children that went through a replacement, how
+        many of them were dropped as duplicates, and the distinct genomes of the
+        population (the i with tt_genome_first's first[i] == i), as Python ints.
+        Pending sub-batches are replaced first; synchronises."""
+        import torch
+        if not self.unique:
+            raise ValueError("unique_stats() needs Island(unique=True)")
+        self.flush()
+        with self._on_stream():
+            first = self.dp.genome_first(self.pop["slot"], self.pop["room"])
+            distinct = (first == torch.arange(self.N, dtype=torch.int32, device=first.device)).sum()
+            dropped = self._dropped.clone()
+        self.sync()
+        return {"children": int(self._replaced), "dropped": int(dropped.item()), "distinct": int(distinct.item())}
 
     def flush(self):
         """Replace the pending sub-batches in order, and make the island's stream
@@ -444,7 +503,7 @@ class Island(Members):
             m[3] = last.work[off:off + 4].view(torch.int32)[0]
             host.copy_(m, non_blocking=True)
             ev.record()
-        snap = Snapshot(host, ev, self.generation, self.N - last.n, self.N, last.off)
+        snap = Snapshot(host, ev, self.generation, *self._source_range(last), last.off)
         self._snap_owner[i] = snap
         return snap
 
@@ -457,8 +516,8 @@ class Island(Members):
         self.sync()
         last = self._parts[self._last_replace]
         src = self.dp.ga_work_source(last.work, self.N)
-        k = self.N - last.n
-        return last.off + src - k if self.generation > 0 and k <= src < self.N else 0
+        k, n = self._source_range(last)
+        return last.off + src - k if self.generation > 0 and k <= src < n else 0
 
 
 class Snapshot:
@@ -537,6 +596,13 @@ def solution_line(best: dict, proc_id: int, total_time: float) -> str:
     else:
         sol["totalBest"] = int(best["hcv"]) * 1000000 + int(best["scv"])
     return json_line({"solution": sol})
+
+
+def unique_line(stats: dict, proc_id: int, island: int) -> str:
+    """The drivers' --unique line of one island: Island.unique_stats() plus
+    the island's global id (procID) and its index within the process."""
+    return json_line({"unique": {"children": int(stats["children"]), "distinct": int(stats["distinct"]),
+                                 "dropped": int(stats["dropped"]), "island": int(island), "procID": int(proc_id)}})
 
 
 def run_final_line(procs: int, threads: int, total_time: float) -> str:

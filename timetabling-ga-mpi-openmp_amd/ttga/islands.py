@@ -15,6 +15,11 @@ Reference correspondence:
   `--report` (after the solution lines, one `report` line per island of the
   process: the best member's six constraint parts, their sums over the
   population and its slot diversity, ttga.report),
+  `--unique` (duplicate-free replacement, ttga.ga.Island(unique=True): a child
+  already in the population is dropped; after the solution lines and before
+  any report line, one `unique` line per island of the process: children
+  bred, children dropped, distinct genomes left. Migration is unchanged: a
+  migrant may duplicate a member of its destination),
   `--stagger` / `--stagger-parts P` (the children of a generation as 2 / P
   sub-batches on as many streams, each bred P - 1 sub-batches behind:
   ttga.ga.Island's staggered schedule),
@@ -60,6 +65,9 @@ def parse_control(argv, out=sys.stdout, err=sys.stderr) -> dict:
     if "--report" in args:                # a population report line per island (ttga.report)
         args.remove("--report")
         extra["report"] = True
+    if "--unique" in args:                # duplicate-free replacement (include/ttga_unique.h)
+        args.remove("--unique")
+        extra["unique"] = True
     for k in ("--pop", "--children", "--generations", "--islands", "--stagger-parts"):
         if k in args:
             i = args.index(k)
@@ -206,7 +214,7 @@ def main(argv=None):
     import torch.distributed as dist
 
     from . import instance as tim
-    from .ga import CostLog, Island, max_steps_for, run_best_line, run_final_line, solution_line
+    from .ga import CostLog, Island, max_steps_for, run_best_line, run_final_line, solution_line, unique_line
 
     from .native import DeviceProblem
 
@@ -257,7 +265,8 @@ def main(argv=None):
     parts = min(C, ctl.get("stagger_parts", ctl.get("stagger", 0)))
     islands = [Island(dp, pop_size=N, children=C, max_steps=max_steps_for(ctl["problem_type"]),
                       seed=rank_seed(seed, rank * K + k), p1=ctl["p1"], p2=ctl["p2"], p3=ctl["p3"],
-                      stream=streams[k], schedule="staggered" if parts >= 2 else "batch", parts=max(parts, 2))
+                      stream=streams[k], schedule="staggered" if parts >= 2 else "batch", parts=max(parts, 2),
+                      unique=bool(ctl.get("unique")))
                for k in range(K)]
     if rank == 0:
         islands[0].initialize()
@@ -303,6 +312,9 @@ def main(argv=None):
         out.write(run_best_line(vals[0][0], gmin) + "\n")
     for k, isl in enumerate(islands):
         out.write(solution_line(isl.member(0), rank * K + k, time.perf_counter() - t_begin) + "\n")
+    if ctl.get("unique"):
+        for k, isl in enumerate(islands):
+            out.write(unique_line(isl.unique_stats(), rank * K + k, k) + "\n")
     if ctl.get("report"):
         from .report import report_line
         for k, isl in enumerate(islands):

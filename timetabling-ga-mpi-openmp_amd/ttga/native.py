@@ -31,6 +31,9 @@ EXPORTS = (
 REPORT_EXPORTS = ("tt_eval_parts", "tt_slot_histogram")
 PART_NAMES = ("room_pairs", "corr_pairs", "unsuitable", "last_slot", "consecutive", "single_class")
 
+# include/ttga_unique.h
+UNIQUE_EXPORTS = ("tt_genome_work_bytes", "tt_genome_first", "tt_ga_unique_work_bytes", "tt_ga_replace_unique")
+
 _lib = None
 
 
@@ -82,6 +85,14 @@ def load(path: os.PathLike | str | None = None) -> ctypes.CDLL:
     lib.tt_slot_histogram.argtypes = [vp, vp, i32, vp, vp]
     for name in REPORT_EXPORTS:
         getattr(lib, name).restype = ctypes.c_int
+    lib.tt_genome_work_bytes.argtypes = [i32, i32]
+    lib.tt_genome_work_bytes.restype = ctypes.c_size_t
+    lib.tt_genome_first.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp]
+    lib.tt_genome_first.restype = ctypes.c_int
+    lib.tt_ga_unique_work_bytes.argtypes = [i32, i32, i32]
+    lib.tt_ga_unique_work_bytes.restype = ctypes.c_size_t
+    lib.tt_ga_replace_unique.argtypes = [vp] * 7 + [i32] + [vp] * 6 + [i32, vp, vp, i32, vp, vp]
+    lib.tt_ga_replace_unique.restype = ctypes.c_int
     for name in EXPORTS:
         if name not in ("tt_last_error", "tt_ga_work_bytes", "tt_ga_work_source_offset"):
             getattr(lib, name).restype = ctypes.c_int
@@ -323,6 +334,58 @@ class DeviceProblem:
             pop["scv"].data_ptr(), pop["feasible"].data_ptr(), pop["penalty"].data_ptr(), N,
             c["slot"].data_ptr(), c["room"].data_ptr(), c["hcv"].data_ptr(), c["scv"].data_ptr(),
             c["feasible"].data_ptr(), c["penalty"].data_ptr(), C, work.data_ptr(), self._stream(pop["slot"])))
+
+    # -- duplicate-free replacement (include/ttga_unique.h) ---------------------------
+    def genome_first(self, slot, room, hash_bits: int = 0):
+        """tt_genome_first: int32 [P], first[i] = the lowest j <= i whose genome
+        (slot row + room row) equals i's; first[i] == i for the first of each kind."""
+        import torch
+        P = self._pop(slot, room)
+        first = torch.empty(P, dtype=torch.int32, device=slot.device)
+        work = torch.empty(int(self.lib.tt_genome_work_bytes(P, self.E)), dtype=torch.uint8, device=slot.device)
+        _check(self.lib, self.lib.tt_genome_first(self.handle, slot.data_ptr(), room.data_ptr(), P, first.data_ptr(),
+                                                  int(hash_bits), ctypes.c_void_p(work.data_ptr() if P else None),
+                                                  self._stream(slot)))
+        return first
+
+    def ga_unique_work(self, N, C):
+        """Work buffer of ga_replace_unique for N members and up to C children."""
+        import torch
+        return torch.empty(int(self.lib.tt_ga_unique_work_bytes(N, C, self.E)), dtype=torch.uint8,
+                           device=torch.device("cuda", self.device))
+
+    def ga_replace_unique(self, pop, child, work, keep=None, n_kept=None, hash_bits: int = 0):
+        """tt_ga_replace_unique: ga_replace with the children dropped whose genome
+        is already in the population or in a child with a lower index. Returns
+        (keep uint8 [C], n_kept int32 [1]) device tensors; ga_work_source(work, N)
+        is then a member's old position p < N or N + c for child c. `work` comes
+        from ga_unique_work(N, C') with C' >= C."""
+        import torch
+        N = self._pop(pop["slot"], pop["room"])
+        C = self._pop(child["slot"], child["room"]) if child is not None else 0
+        dev = pop["slot"].device
+        if keep is None:
+            keep = torch.empty(C, dtype=torch.uint8, device=dev)
+        elif not (keep.is_cuda and keep.dtype == torch.uint8 and keep.is_contiguous() and tuple(keep.shape) == (C,)
+                  and keep.device == dev):
+            raise ValueError("keep must be a contiguous uint8 CUDA tensor of shape [C] on the population's device")
+        if n_kept is None:
+            n_kept = torch.empty(1, dtype=torch.int32, device=dev)
+        elif not (n_kept.is_cuda and n_kept.dtype == torch.int32 and n_kept.is_contiguous() and n_kept.numel() == 1
+                  and n_kept.device == dev):
+            raise ValueError("n_kept must be a contiguous int32 CUDA tensor of one entry on the population's device")
+        if not (work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous() and work.device == dev
+                and work.numel() >= int(self.lib.tt_ga_unique_work_bytes(N, C, self.E))):
+            raise ValueError("work must be a uint8 CUDA tensor of at least tt_ga_unique_work_bytes(N, C, E) bytes")
+        c = child or {k: pop[k] for k in pop}
+        _check(self.lib, self.lib.tt_ga_replace_unique(
+            self.handle, pop["slot"].data_ptr(), pop["room"].data_ptr(), pop["hcv"].data_ptr(),
+            pop["scv"].data_ptr(), pop["feasible"].data_ptr(), pop["penalty"].data_ptr(), N,
+            c["slot"].data_ptr(), c["room"].data_ptr(), c["hcv"].data_ptr(), c["scv"].data_ptr(),
+            c["feasible"].data_ptr(), c["penalty"].data_ptr(), C,
+            ctypes.c_void_p(keep.data_ptr() if C else None), n_kept.data_ptr(), int(hash_bits), work.data_ptr(),
+            self._stream(pop["slot"])))
+        return keep, n_kept
 
     @staticmethod
     def _rng(rng, P):

@@ -24,12 +24,15 @@ slots, rooms, hcv, scv, feasible, penalty and final RNG states
 
     python tools/bench_ga.py [--config comp01] [--pop 65536] [--children 65536]
                              [--gens 3] [--steps 200] [--cpu-sample 512]
-                             [--warm-gens N] [--warm-feasible F]
+                             [--warm-gens N] [--warm-feasible F] [--unique]
 
 --warm-gens / --warm-feasible run untimed generations first, until a fraction F
 of the population is feasible (or N generations), so the timed generations
 are the GA's phase-2 regime (feasible parents, localSearch phase 2), where the
-reference spends most of a run.
+reference spends most of a run. --unique runs Island(unique=True) (a child
+already in the population is dropped) and adds the children bred, dropped and
+the distinct genomes left ("unique"); its populations part from the plain
+run's at the first dropped child, so the two runs' times are not like for like.
 """
 import argparse
 import json
@@ -80,6 +83,7 @@ def parser():
     ap.add_argument("--islands", type=int, default=1,
                     help="K independent islands of --pop members on this GPU, each on its own stream (ttga.islands "
                          "--islands K between migrations); children/s over all K")
+    ap.add_argument("--unique", action="store_true", help="duplicate-free replacement (Island(unique=True))")
     return ap
 
 
@@ -92,7 +96,7 @@ def run_ga(a):
     seeds = [a.seed] + [rank_seed(a.seed, k) for k in range(1, K)]
     isls = [Island(dp, pop_size=a.pop, children=a.children, max_steps=a.steps, seed=seeds[k],
                    lpt=None if a.lpt == "auto" else a.lpt == "on", stream=torch.cuda.Stream() if K > 1 else None,
-                   schedule=a.schedule, parts=a.parts)
+                   schedule=a.schedule, parts=a.parts, unique=a.unique)
             for k in range(K)]
     isl = isls[0]
     torch.cuda.synchronize()
@@ -154,6 +158,10 @@ def run_ga(a):
            "best": {"feasible": feas, "scv": scv, "hcv": hcv, "penalty": pen},
            "feasible_fraction": float(isl.pop["feasible"].float().mean().item())}
 
+    if a.unique:
+        stats = [i.unique_stats() for i in isls]
+        out["unique"] = {k: sum(s[k] for s in stats) for k in ("children", "dropped", "distinct")}
+        out["unique"]["dropped_share"] = out["unique"]["dropped"] / max(1, out["unique"]["children"])
     R = ref()
     if R is not None and a.cpu_sample > 0:
         n = min(a.cpu_sample, a.children)

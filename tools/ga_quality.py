@@ -19,6 +19,11 @@ rate (Fisher exact test), best-scv distribution (Mann-Whitney U, two-sided),
 medians of the logged best at generation checkpoints, and wall time per run.
 
     python tools/ga_quality.py [--config sm] [--seeds 16] [--gens 2001] [--steps 200] [--pop 10]
+
+--unique compares the device GA with itself instead: Island(unique=True)
+(duplicate-free replacement) against the plain island, same seeds and
+parameters, no reference run: final values (Mann-Whitney U, two-sided), their
+medians, the children dropped and the distinct genomes left per run.
 """
 import argparse
 import json
@@ -47,7 +52,7 @@ def summarize(final, feas, trace, checkpoints):
     }
 
 
-def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch"):
+def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch", unique=False, stats_out=None):
     import torch
 
     from ttga import native
@@ -58,7 +63,8 @@ def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch"):
     trace = np.zeros((len(seeds), gens + 1), np.int64)
     secs = []
     for k, s in enumerate(seeds):
-        isl = Island(dp, pop_size=pop, children=children, max_steps=steps, seed=int(s), schedule=schedule)
+        isl = Island(dp, pop_size=pop, children=children, max_steps=steps, seed=int(s), schedule=schedule,
+                     unique=unique)
         tr = torch.zeros(gens + 1, dtype=torch.int64, device="cuda")
         p = isl.pop
 
@@ -80,6 +86,12 @@ def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch"):
         trace[k] = tr.cpu().numpy()
         feas[k] = 1 if isl.member_meta(0)[0] else 0
         final[k] = trace[k, -1]
+        if stats_out is not None:
+            if unique:
+                stats_out.append(isl.unique_stats())
+            else:            # the plain island's distinct genomes, for the comparison
+                first = dp.genome_first(isl.pop["slot"], isl.pop["room"])
+                stats_out.append({"distinct": int((first == torch.arange(pop, dtype=torch.int32, device="cuda")).sum())})
     return final, feas, trace, float(np.mean(secs))
 
 
@@ -97,6 +109,8 @@ def main():
     ap.add_argument("--device-gens", type=int, default=0, help="device generations (0: --gens)")
     ap.add_argument("--device-schedule", choices=["batch", "staggered"], default="batch")
     ap.add_argument("--no-ref-as-is", action="store_true", help="skip the reference run with F2")
+    ap.add_argument("--unique", action="store_true",
+                    help="compare Island(unique=True) with the plain island (no reference run)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     from scipy import stats
@@ -118,6 +132,28 @@ def main():
     res = {"config": a.config, "E": inst.E, "R": inst.R, "F": inst.F, "S": inst.S, "pop_size": a.pop,
            "children_per_generation": 1, "generations": a.gens, "max_steps": a.steps, "seeds": seeds,
            "runs": {}}
+    if a.unique:
+        dg = a.device_gens or a.gens
+        res["children_per_generation"], res["generations"] = a.device_children, dg
+        for name, uniq in (("device", False), ("device_unique", True)):
+            st = []
+            final, feas, trace, secs = device_runs(inst, seeds, a.pop, dg, a.steps, a.device_children,
+                                                   a.device_schedule, uniq, st)
+            res["runs"][name] = summarize(final, feas, trace, sorted({0, dg // 2, dg}))
+            res["runs"][name]["seconds_per_run"] = secs
+            res["runs"][name]["distinct"] = [s["distinct"] for s in st]
+            if uniq:
+                res["runs"][name]["dropped"] = [s["dropped"] for s in st]
+                res["runs"][name]["children"] = st[0]["children"]
+        vp, vu = (np.array(res["runs"][n]["final_log_value"]) for n in ("device", "device_unique"))
+        same = bool(np.array_equal(vp, vu))
+        res["tests"] = {"unique_vs_plain": {
+            "final_value_mannwhitney_p": 1.0 if same else float(stats.mannwhitneyu(vu, vp, alternative="two-sided").pvalue),
+            "median_unique": float(np.median(vu)), "median_plain": float(np.median(vp))}}
+        print(json.dumps(res), flush=True)
+        if a.out:
+            pathlib.Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
+        return
     R = ref()
     if R is None:
         raise SystemExit("oracle/_ref/libttref.so is missing (build it where /root/reference exists)")
