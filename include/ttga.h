@@ -22,6 +22,11 @@
  * Limits: 1 <= E <= 65535, 1 <= R <= 64, S >= 0, F >= 0; at most 256 events
  * share one timeslot inside tt_assign_rooms/tt_local_search (beyond that the
  * affected rooms are written as 255 and tt_device_status() reports it).
+ * A kernel whose LDS image of the instance does not fit returns TT_ERR_LIMIT
+ * and launches nothing: tt_random_init stages 64 slot rows (E <= 2560),
+ * tt_crossover 64 rows of each parent (E <= 1280); tt_local_search, and
+ * tt_assign_rooms / tt_mutation at R <= 16, keep about 11 to 13 bytes per
+ * event and fit up to roughly 12,000 events.
  */
 #ifndef TTGA_H
 #define TTGA_H
@@ -81,7 +86,7 @@ int tt_eval(const tt_problem* p, const uint8_t* slot, const uint8_t* room, int P
  *         lane-per-individual phase (attendance masks) and a wave-per-individual
  *         phase (bitset hard constraints), slot rows staged by LDS-DMA,
  *   13 = wide path: eval_lanes (16-wave lane-phase tile) + eval_corr (batches
- *        of individuals against the streamed correlation triangle; E <= 2490,
+ *        of individuals against the streamed correlation triangle; E <= 2491,
  *        the 64-row tile must fit the LDS; automatic for E > 448).
  * Bits 4 and up of `variant` are profiling switches (csrc/tt_eval.hip); most
  * of them give invalid results. All variants give identical results. */
@@ -89,7 +94,7 @@ int tt_eval_variant(const tt_problem* p, const uint8_t* slot, const uint8_t* roo
                     int32_t* scv, uint8_t* feasible, int32_t* penalty, int variant, void* stream);
 
 /* The variant tt_eval chooses for this instance: 8 or 7 (E <= 448), 13 (the
- * wide path, E <= 2490), else 2 (eval_block); -1 for a null handle. */
+ * wide path, E <= 2491), else 2 (eval_block); -1 for a null handle. */
 int tt_eval_auto_variant(const tt_problem* p);
 
 /* Solution::assignRooms (Solution.cpp:772-891) on every non-empty timeslot in

@@ -7,6 +7,7 @@ util.cpp from /root/reference compiled unmodified, F1 neutralised by
 synthetic instances and populations (real .tim files are unavailable offline).
 
     make -C oracle && python oracle/gen_golden.py
+    python oracle/gen_golden.py move3      # tests/golden/move3.npz alone
 
 The fixtures are data only (inputs + reference outputs, compressed npz).
 """
@@ -127,5 +128,54 @@ def main():
               f"unmatched-possible rooms {int((poss.sum(1) == 0).sum())} events without a room")
 
 
+def move3():
+    """tests/golden/move3.npz: the reference's localSearch with Move3 enabled,
+    from 8 RandomInitialSolution rows (phase 1) and 8 feasible rows (phase 2)
+    of two instances (tests/move3_cases.py: GOLDEN_SHAPES, GOLDEN_CASES). The
+    feasible rows are those of move3_cases.starts() on the reference, the ones
+    that the reference's Move3-only case changes first, so that accepted
+    Move3s of phase 2 are in the fixture."""
+    import move3_cases as mc
+    R = ref()
+    if R is None:
+        sys.exit("oracle/_ref/libttref.so not built (needs /root/reference): make -C oracle ref")
+    OUT.mkdir(parents=True, exist_ok=True)
+    n = mc.GOLDEN_ROWS
+    data = {}
+    for tag, key in mc.GOLDEN_SHAPES.items():
+        inst = mc.instance(key)
+        h = R.problem(inst)
+        st = mc.starts(h, key)
+        data.update({f"{tag}_dims": np.array([inst.E, inst.R, inst.F, inst.S], np.int32),
+                     f"{tag}_room_size": inst.room_size,
+                     f"{tag}_student_bits": np.packbits(inst.student_events.astype(np.uint8), axis=1),
+                     f"{tag}_room_features": inst.room_features.astype(np.uint8),
+                     f"{tag}_event_features": inst.event_features.astype(np.uint8)})
+        for w in "ab":
+            s0, r0 = st[w]
+            seeds = mc.run_seeds(key, w, s0.shape[0])
+            pick = np.arange(n)
+            if w == "b":
+                p, steps = mc.GOLDEN_CASES[0]
+                s1, r1, _ = h.local_search(s0, r0, seeds, steps, *p)
+                moved = (s0 != s1).any(1) | (r0 != r1).any(1)
+                pick = np.sort(np.argsort(~moved, kind="stable")[:n])
+            s0, r0, seeds = s0[pick], r0[pick], seeds[pick]
+            assert s0.shape[0] == n
+            data.update({f"{tag}_{w}_slots": s0, f"{tag}_{w}_rooms": r0, f"{tag}_{w}_seeds": seeds})
+            for k, (p, steps) in enumerate(mc.GOLDEN_CASES):
+                s1, r1, g1 = h.local_search(s0, r0, seeds, steps, *p)
+                data.update({f"{tag}_{w}{k}_slots": s1, f"{tag}_{w}{k}_rooms": r1, f"{tag}_{w}{k}_rng": g1})
+                print(f"move3 {tag} {w} {p} x {steps}: {mc.changed_rows(s0, r0, s1, r1)}/{n} rows changed")
+            if w == "b":
+                assert h.eval(s0, r0)[2].all()
+    np.savez_compressed(OUT / "move3.npz", **data)
+    print(f"move3.npz: {(OUT / 'move3.npz').stat().st_size} bytes")
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["move3"]:
+        move3()
+    else:
+        main()
+        move3()

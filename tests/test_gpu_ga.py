@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import ttga
-from helpers import dev, host, json_lines as _json_lines, oracle_population
+from helpers import dev, host, json_lines as _json_lines, oracle_generations, oracle_population
 from oracle_lib import oracle
 
 pytestmark = pytest.mark.gpu
@@ -84,12 +84,7 @@ def test_island_generations_vs_oracle(sm, N, C, gens, lpt):
     for _ in range(gens):
         isl.step()
     pop = oracle_population(o, N, seed, steps)
-    rng = stream_seeds(seed, N, C)
-    for _ in range(gens):
-        cs, cr, fl, rng = o.ga_breed(pop["slot"], pop["room"], pop["penalty"], rng, C, 0.8, 0.5, 1)
-        cs, cr, rng = o.local_search(cs, cr, rng, steps)
-        h, sc, f, p = o.eval(cs, cr)
-        pop = o.ga_replace(pop, dict(slot=cs, room=cr, hcv=h, scv=sc, feasible=f, penalty=p))
+    pop, rng = oracle_generations(o, pop, stream_seeds(seed, N, C), C, gens, steps)
     for k in KEYS:
         assert np.array_equal(host(isl.pop[k]), pop[k]), k
     assert np.array_equal(host(isl.rng_child), rng)

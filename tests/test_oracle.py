@@ -7,8 +7,9 @@ restatement is additionally cross-checked on fresh random inputs.
 import numpy as np
 import pytest
 
+import move3_cases as mc
 import ttga
-from oracle_lib import oracle, ref
+from oracle_lib import oracle, ref, split_rows
 
 NAMES = ["sm", "med", "tight"]
 
@@ -127,6 +128,23 @@ def test_local_search(golden_dir, orc, name):
     assert np.array_equal(g, z["lsp3_rng"])
 
 
+@pytest.mark.parametrize("tag", list(mc.GOLDEN_SHAPES))
+def test_local_search_move3_golden(golden_dir, orc, tag):
+    """Move3 (prob3 > 0) of the oracle against the reference's own localSearch
+    (tests/golden/move3.npz): 8 phase-1 and 8 feasible rows of two instances,
+    Move3 alone for 64 steps, every move for 300, a mix for 300. The fixture
+    holds accepted Move3s of both phases (rows changed with prob1 = prob2 = 0;
+    from the feasible rows on the 300-event instance)."""
+    z = np.load(golden_dir / "move3.npz")
+    inst = mc.golden_instance(z, tag)
+    assert inst.to_tim() == mc.instance(mc.GOLDEN_SHAPES[tag]).to_tim()
+    changed = mc.check_golden(z, tag, orc.problem(inst).local_search)
+    assert changed["a", 0] == mc.GOLDEN_ROWS
+    if tag == "e300":
+        assert changed["b", 0] >= 1
+    assert changed["b", 1] >= 1 and changed["b", 2] >= 1
+
+
 # ---- live cross-checks against the reference build (skipped where it was never built)
 REF = ref()
 needs_ref = pytest.mark.skipif(REF is None, reason="oracle/_ref not built (no /root/reference)")
@@ -192,3 +210,24 @@ def test_oracle_children_vs_reference_per_child_path(orc, name, steps):
     for k, v in exp.items():
         assert np.array_equal(got[k], v), k
     assert np.array_equal(grng, rng)
+
+
+@needs_ref
+@pytest.mark.parametrize("key", mc.SMALL)
+def test_oracle_vs_reference_move3_matrix(orc, key):
+    """The Move3 matrix of tests/test_gpu_ls_move3.py on its two small shapes,
+    run by the reference's own Solution code: phase-1 and feasible starts, the
+    four probability triples. The oracle that checks the GPU there equals the
+    reference here."""
+    inst = mc.instance(key)
+    ho, hr = orc.problem(inst), REF.problem(inst)
+    st = mc.starts(ho, key)
+    for w in "ab":
+        s0, r0 = st[w]
+        seeds = mc.run_seeds(key, w, s0.shape[0])
+        for p, steps in mc.TRIPLES:
+            a = split_rows(ho.local_search, (s0, r0, seeds), steps, *p)
+            b = split_rows(hr.local_search, (s0, r0, seeds), steps, *p)
+            for x, y in zip(a, b):
+                assert np.array_equal(x, y), (w, p)
+            assert mc.changed_rows(s0, r0, a[0], a[1]) > 0, (w, p)
