@@ -27,6 +27,10 @@
  * tt_crossover 64 rows of each parent (E <= 1280); tt_local_search, and
  * tt_assign_rooms / tt_mutation at R <= 16, keep about 11 to 13 bytes per
  * event and fit up to roughly 12,000 events.
+ *
+ * Additions with no counterpart in the reference have headers of their own:
+ * ttga_report.h, ttga_unique.h and ttga_greedy.h (a greedy constructive
+ * initial population, the counterpart of tt_random_init).
  */
 #ifndef TTGA_H
 #define TTGA_H
@@ -217,7 +221,8 @@ int tt_ga_replace(const tt_problem* p, uint8_t* pop_slot, uint8_t* pop_room, int
  *              searched twice concurrently (undefined result);
  *   bit 4 (16) the local search's per-stream redo list overflowed (unreachable:
  *              it holds P entries and a launch lists each wave at most once);
- *              the individuals not listed are left unsearched.
+ *              the individuals not listed are left unsearched;
+ *   bit 5 (32) ttga_greedy.h's tt_greedy_init skipped an order entry outside 0..E-1.
  * Synchronises the device. */
 int tt_device_status(const tt_problem* p, int32_t* status);
 

@@ -11,7 +11,11 @@
 //
 //   ttga-ga -i instance.tim [-s seed] [-p type] [-c children]
 //           [-p1 x -p2 y -p3 z] [--gpus G] [--islands K] [--pop N] [--generations n] [--rccl] [--stagger]
-//           [--report] [--unique]
+//           [--report] [--unique] [--init random|greedy]
+//
+// --init greedy: the initial population is built by tt_greedy_init
+// (include/ttga_greedy.h) instead of RandomInitialSolution (ga.cpp:431); the
+// local search and the sort after it are unchanged. The default is random.
 //
 // --unique: duplicate-free replacement (include/ttga_unique.h): a child whose
 // genome is already in the population, or in an earlier child of its sub-batch,
@@ -69,6 +73,7 @@
 #include <vector>
 
 #include "../../include/ttga_report.h"
+#include "../../include/ttga_greedy.h"
 #include "../../include/ttga_unique.h"
 
 namespace {
@@ -103,6 +108,7 @@ struct Control {
     int stagger = 0;                              // sub-batches of the staggered schedule (0: batch)
     bool report = false;                          // a population report line per island
     bool unique = false;                          // duplicate-free replacement, a unique line per island
+    bool greedy = false;                          // --init greedy: tt_greedy_init builds the initial population
 };
 
 // Control::Control (Control.cpp:3-137) plus the --gpus/--pop/--generations extensions.
@@ -124,6 +130,14 @@ Control parse_control(int argc, char** argv) {
     if (auto it = std::find(args.begin(), args.end(), "--unique"); it != args.end()) {
         c.unique = true;
         args.erase(it);
+    }
+    if (auto it = std::find(args.begin(), args.end(), "--init"); it != args.end()) {
+        if (it + 1 == args.end() || (*(it + 1) != "random" && *(it + 1) != "greedy")) {
+            std::cerr << "Error: --init must be random or greedy" << std::endl;
+            std::exit(1);
+        }
+        c.greedy = *(it + 1) == "greedy";
+        args.erase(it, it + 2);
     }
     for (const char* k : {"--gpus", "--islands", "--pop", "--generations", "--children", "--stagger-parts"}) {
         auto it = std::find(args.begin(), args.end(), k);
@@ -504,6 +518,7 @@ struct Island {
     // kept count in kept_log[r] on the device (the initial sort, C = 0, has none), read once
     // at the end, so no generation waits for it; children = those that went through a replacement
     bool unique = false;
+    bool greedy = false;                              // --init greedy
     uint8_t* keep = nullptr;                          // [C], part j's flags at keep + off
     int32_t* kept_log = nullptr;
     long kept_cap = 0, kept_used = 0, children = 0;
@@ -571,7 +586,20 @@ struct Island {
 
     // ga.cpp:429-434 for every member, then the population is sorted
     void initialize() {
-        check_tt(tt_random_init(tp, rng_init, pop.slot, pop.room, N, st), "tt_random_init");
+        if (greedy) {
+            // the event order and its scratch are needed once: freed when the stream has used them
+            int32_t* ev_order = nullptr;
+            void* ev_work = nullptr;
+            check_hip(hipMalloc(&ev_order, 4 * (size_t)E), "hipMalloc");
+            check_hip(hipMalloc(&ev_work, tt_greedy_work_bytes(tp)), "hipMalloc");
+            check_tt(tt_greedy_order(tp, ev_order, ev_work, st), "tt_greedy_order");
+            check_tt(tt_greedy_init(tp, ev_order, rng_init, pop.slot, pop.room, N, st), "tt_greedy_init");
+            check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
+            check_hip(hipFree(ev_order), "hipFree");
+            check_hip(hipFree(ev_work), "hipFree");
+        } else {
+            check_tt(tt_random_init(tp, rng_init, pop.slot, pop.room, N, st), "tt_random_init");
+        }
         check_tt(tt_local_search_eval(tp, pop.slot, pop.room, rng_init, N, max_steps, p1, p2, p3, nullptr, pop.hcv,
                                       pop.scv, pop.feasible, pop.penalty, st),
                  "tt_local_search_eval");
@@ -846,6 +874,7 @@ int main(int argc, char** argv) {
         I.p1 = ctl.p1; I.p2 = ctl.p2; I.p3 = ctl.p3;
         I.parts = ctl.stagger >= 2 ? std::min(ctl.stagger, C) : 1;
         I.unique = ctl.unique;
+        I.greedy = ctl.greedy;
     }
     std::vector<ncclComm_t> comms(K, nullptr);
     if (rccl) {

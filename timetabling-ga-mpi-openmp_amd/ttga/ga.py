@@ -189,6 +189,11 @@ class Island(Members):
     the caller's next reads and writes of the population are ordered as on a
     one-part island.
 
+    init="greedy": initialize() builds the members with tt_greedy_init
+    (include/ttga_greedy.h) instead of tt_random_init; the local search, the
+    sort and everything after it are the same, and so are breeding (its
+    skip_init_draws included) and migration.
+
     unique=True: every replacement is tt_ga_replace_unique (include/ttga_unique.h):
     a child whose genome (slot row + room row) equals a member's or an earlier
     child's of the same sub-batch is dropped, decided on the device with no
@@ -201,7 +206,7 @@ class Island(Members):
     def __init__(self, dp, pop_size: int = 10, children: int = 1, max_steps: int = 200, seed: int = 1,
                  p_cross: float = 0.8, p_mut: float = 0.5, skip_init_draws: bool = True, device=None,
                  p1: float = 1.0, p2: float = 1.0, p3: float = 0.0, lpt: bool | None = None, stream=None,
-                 schedule: str = "batch", parts: int = 2, unique: bool = False):
+                 schedule: str = "batch", parts: int = 2, unique: bool = False, init: str = "random"):
         """stream: a torch.cuda.Stream of the island's own, or None (torch's current
         stream). Islands multiplexed on one GPU (ttga.islands --islands K) each take
         one, so one island's launches fill the SIMD slots another's local-search tail
@@ -209,6 +214,8 @@ class Island(Members):
         synchronises its stream first, and a caller that moves data between islands
         (migration) synchronises the device around it."""
         import torch
+        if init not in ("random", "greedy"):
+            raise ValueError("init must be 'random' or 'greedy'")
         if not (1 <= children <= pop_size):
             raise ValueError("need 1 <= children <= pop_size")
         if schedule not in ("batch", "staggered"):
@@ -229,6 +236,7 @@ class Island(Members):
         self.rng_init = torch.from_numpy(stream_seeds(seed, 0, self.N)).to(dev)
         self.rng_child = torch.from_numpy(stream_seeds(seed, self.N, self.C)).to(dev)
         self.unique = bool(unique)
+        self.init = init
         self.generation = 0
         self.schedule = schedule
         self.parts = int(parts) if schedule == "staggered" else 1
@@ -369,11 +377,16 @@ class Island(Members):
         self.dp.eval(p["slot"], p["room"], out=(p["hcv"], p["scv"], p["feasible"], p["penalty"]))
 
     def initialize(self):
-        """ga.cpp:429-434 for every member, then the population is sorted."""
+        """ga.cpp:429-434 for every member, then the population is sorted; with
+        init "greedy" the members start from tt_greedy_init instead of
+        RandomInitialSolution (ga.cpp:431)."""
         self._fork()
         with self._on_stream():
             p = self.pop
-            self.dp.random_init(self.rng_init, p["slot"], p["room"])
+            if self.init == "greedy":
+                self.dp.greedy_init(self.rng_init, p["slot"], p["room"])
+            else:
+                self.dp.random_init(self.rng_init, p["slot"], p["room"])
             self.dp.local_search(p["slot"], p["room"], self.rng_init, self.max_steps, self.p1, self.p2, self.p3,
                                  out=(p["hcv"], p["scv"], p["feasible"], p["penalty"]))
             if self.unique:

@@ -20,6 +20,9 @@ Reference correspondence:
   any report line, one `unique` line per island of the process: children
   bred, children dropped, distinct genomes left. Migration is unchanged: a
   migrant may duplicate a member of its destination),
+  `--init random|greedy` (greedy: the initial population is built by
+  tt_greedy_init, include/ttga_greedy.h, instead of RandomInitialSolution;
+  the default is random),
   `--stagger` / `--stagger-parts P` (the children of a generation as 2 / P
   sub-batches on as many streams, each bred P - 1 sub-batches behind:
   ttga.ga.Island's staggered schedule),
@@ -73,6 +76,13 @@ def parse_control(argv, out=sys.stdout, err=sys.stderr) -> dict:
             i = args.index(k)
             extra[k[2:].replace("-", "_")] = int(args[i + 1])
             del args[i:i + 2]
+    if "--init" in args:                  # the initial population (include/ttga_greedy.h)
+        i = args.index("--init")
+        if i + 1 >= len(args) or args[i + 1] not in ("random", "greedy"):
+            err.write("Error: --init must be random or greedy\n")
+            raise SystemExit(1)
+        extra["init"] = args[i + 1]
+        del args[i:i + 2]
     if len(args) % 2 != 0:
         err.write("Parse error: Number of command line parameters incorrect\nUsage:\n" + USAGE + "\n")
         raise SystemExit(1)
@@ -266,7 +276,7 @@ def main(argv=None):
     islands = [Island(dp, pop_size=N, children=C, max_steps=max_steps_for(ctl["problem_type"]),
                       seed=rank_seed(seed, rank * K + k), p1=ctl["p1"], p2=ctl["p2"], p3=ctl["p3"],
                       stream=streams[k], schedule="staggered" if parts >= 2 else "batch", parts=max(parts, 2),
-                      unique=bool(ctl.get("unique")))
+                      unique=bool(ctl.get("unique")), init=ctl.get("init", "random"))
                for k in range(K)]
     if rank == 0:
         islands[0].initialize()

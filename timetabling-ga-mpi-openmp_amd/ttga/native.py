@@ -34,6 +34,9 @@ PART_NAMES = ("room_pairs", "corr_pairs", "unsuitable", "last_slot", "consecutiv
 # include/ttga_unique.h
 UNIQUE_EXPORTS = ("tt_genome_work_bytes", "tt_genome_first", "tt_ga_unique_work_bytes", "tt_ga_replace_unique")
 
+# include/ttga_greedy.h
+GREEDY_EXPORTS = ("tt_greedy_work_bytes", "tt_greedy_order", "tt_greedy_init")
+
 _lib = None
 
 
@@ -93,6 +96,12 @@ def load(path: os.PathLike | str | None = None) -> ctypes.CDLL:
     lib.tt_ga_unique_work_bytes.restype = ctypes.c_size_t
     lib.tt_ga_replace_unique.argtypes = [vp] * 7 + [i32] + [vp] * 6 + [i32, vp, vp, i32, vp, vp]
     lib.tt_ga_replace_unique.restype = ctypes.c_int
+    lib.tt_greedy_work_bytes.argtypes = [vp]
+    lib.tt_greedy_work_bytes.restype = ctypes.c_size_t
+    lib.tt_greedy_order.argtypes = [vp, vp, vp, vp]
+    lib.tt_greedy_order.restype = ctypes.c_int
+    lib.tt_greedy_init.argtypes = [vp, vp, vp, vp, vp, i32, vp]
+    lib.tt_greedy_init.restype = ctypes.c_int
     for name in EXPORTS:
         if name not in ("tt_last_error", "tt_ga_work_bytes", "tt_ga_work_source_offset"):
             getattr(lib, name).restype = ctypes.c_int
@@ -386,6 +395,39 @@ class DeviceProblem:
             ctypes.c_void_p(keep.data_ptr() if C else None), n_kept.data_ptr(), int(hash_bits), work.data_ptr(),
             self._stream(pop["slot"])))
         return keep, n_kept
+
+    # -- greedy constructive initial population (include/ttga_greedy.h) ----------------
+    def greedy_order(self):
+        """tt_greedy_order: the events hardest first (int32 [E] CUDA tensor),
+        computed on first use on torch's current stream and kept on the object."""
+        import torch
+        if getattr(self, "_greedy_order", None) is None:
+            dev = torch.device("cuda", self.device)
+            order = torch.empty(self.E, dtype=torch.int32, device=dev)
+            work = torch.empty(int(self.lib.tt_greedy_work_bytes(self.handle)), dtype=torch.uint8, device=dev)
+            _check(self.lib, self.lib.tt_greedy_order(self.handle, order.data_ptr(), work.data_ptr(),
+                                                      self._stream(order)))
+            self._greedy_order = order
+            self._greedy_order_ev = torch.cuda.Event()
+            self._greedy_order_ev.record(torch.cuda.current_stream(dev))
+        else:
+            # a later use may be on another stream than the one that computed it
+            torch.cuda.current_stream(self._greedy_order.device).wait_event(self._greedy_order_ev)
+        return self._greedy_order
+
+    def greedy_init(self, rng, slot, room, order=None):
+        """tt_greedy_init: the counterpart of random_init; `order` (int32 [E] CUDA
+        tensor, a permutation of the events) defaults to greedy_order()."""
+        import torch
+        P = self._pop(slot, room)
+        self._rng(rng, P)
+        if order is None:
+            order = self.greedy_order()
+        elif not (order.is_cuda and order.dtype == torch.int32 and order.is_contiguous() and order.numel() == self.E
+                  and order.device == slot.device):
+            raise ValueError("order must be a contiguous int32 CUDA tensor of E entries on the population's device")
+        _check(self.lib, self.lib.tt_greedy_init(self.handle, order.data_ptr(), rng.data_ptr(), slot.data_ptr(),
+                                                 room.data_ptr(), P, self._stream(slot)))
 
     @staticmethod
     def _rng(rng, P):

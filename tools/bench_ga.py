@@ -25,6 +25,7 @@ slots, rooms, hcv, scv, feasible, penalty and final RNG states
     python tools/bench_ga.py [--config comp01] [--pop 65536] [--children 65536]
                              [--gens 3] [--steps 200] [--cpu-sample 512]
                              [--warm-gens N] [--warm-feasible F] [--unique]
+                             [--init random|greedy]
 
 --warm-gens / --warm-feasible run untimed generations first, until a fraction F
 of the population is feasible (or N generations), so the timed generations
@@ -33,6 +34,9 @@ reference spends most of a run. --unique runs Island(unique=True) (a child
 already in the population is dropped) and adds the children bred, dropped and
 the distinct genomes left ("unique"); its populations part from the plain
 run's at the first dropped child, so the two runs' times are not like for like.
+--init greedy builds the initial population with tt_greedy_init
+(include/ttga_greedy.h, Island(init="greedy")) instead of tt_random_init; the
+record then carries "init" and the feasible share right after initialize().
 """
 import argparse
 import json
@@ -84,6 +88,8 @@ def parser():
                     help="K independent islands of --pop members on this GPU, each on its own stream (ttga.islands "
                          "--islands K between migrations); children/s over all K")
     ap.add_argument("--unique", action="store_true", help="duplicate-free replacement (Island(unique=True))")
+    ap.add_argument("--init", choices=["random", "greedy"], default="random",
+                    help="the initial population: tt_random_init or tt_greedy_init (Island(init=...))")
     return ap
 
 
@@ -96,7 +102,7 @@ def run_ga(a):
     seeds = [a.seed] + [rank_seed(a.seed, k) for k in range(1, K)]
     isls = [Island(dp, pop_size=a.pop, children=a.children, max_steps=a.steps, seed=seeds[k],
                    lpt=None if a.lpt == "auto" else a.lpt == "on", stream=torch.cuda.Stream() if K > 1 else None,
-                   schedule=a.schedule, parts=a.parts, unique=a.unique)
+                   schedule=a.schedule, parts=a.parts, unique=a.unique, init=a.init)
             for k in range(K)]
     isl = isls[0]
     torch.cuda.synchronize()
@@ -105,6 +111,7 @@ def run_ga(a):
         i.initialize()
     torch.cuda.synchronize()
     init_s = time.perf_counter() - t0
+    feas_init = min(float(i.pop["feasible"].float().mean().item()) for i in isls)
     for i in isls:
         i.step()                                # warm-up generation
     torch.cuda.synchronize()
@@ -158,6 +165,9 @@ def run_ga(a):
            "best": {"feasible": feas, "scv": scv, "hcv": hcv, "penalty": pen},
            "feasible_fraction": float(isl.pop["feasible"].float().mean().item())}
 
+    if a.init != "random":
+        out["init"] = a.init
+        out["feasible_fraction_after_init"] = feas_init
     if a.unique:
         stats = [i.unique_stats() for i in isls]
         out["unique"] = {k: sum(s[k] for s in stats) for k in ("children", "dropped", "distinct")}

@@ -24,6 +24,11 @@ medians of the logged best at generation checkpoints, and wall time per run.
 (duplicate-free replacement) against the plain island, same seeds and
 parameters, no reference run: final values (Mann-Whitney U, two-sided), their
 medians, the children dropped and the distinct genomes left per run.
+
+--init greedy does the same for the initial population: Island(init="greedy")
+(tt_greedy_init, include/ttga_greedy.h) against the plain island, same seeds
+and parameters, no reference run: final values (Mann-Whitney U, two-sided),
+their medians, and the medians of the logged best at generation checkpoints.
 """
 import argparse
 import json
@@ -52,7 +57,8 @@ def summarize(final, feas, trace, checkpoints):
     }
 
 
-def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch", unique=False, stats_out=None):
+def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch", unique=False, stats_out=None,
+                init="random"):
     import torch
 
     from ttga import native
@@ -64,7 +70,7 @@ def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch", uni
     secs = []
     for k, s in enumerate(seeds):
         isl = Island(dp, pop_size=pop, children=children, max_steps=steps, seed=int(s), schedule=schedule,
-                     unique=unique)
+                     unique=unique, init=init)
         tr = torch.zeros(gens + 1, dtype=torch.int64, device="cuda")
         p = isl.pop
 
@@ -111,6 +117,8 @@ def main():
     ap.add_argument("--no-ref-as-is", action="store_true", help="skip the reference run with F2")
     ap.add_argument("--unique", action="store_true",
                     help="compare Island(unique=True) with the plain island (no reference run)")
+    ap.add_argument("--init", choices=["random", "greedy"], default="random",
+                    help="greedy: compare Island(init='greedy') with the plain island (no reference run)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     from scipy import stats
@@ -150,6 +158,24 @@ def main():
         res["tests"] = {"unique_vs_plain": {
             "final_value_mannwhitney_p": 1.0 if same else float(stats.mannwhitneyu(vu, vp, alternative="two-sided").pvalue),
             "median_unique": float(np.median(vu)), "median_plain": float(np.median(vp))}}
+        print(json.dumps(res), flush=True)
+        if a.out:
+            pathlib.Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
+        return
+    if a.init == "greedy":
+        dg = a.device_gens or a.gens
+        res["children_per_generation"], res["generations"] = a.device_children, dg
+        cps = sorted({0, 1, 10, 100, dg // 2, dg} & set(range(dg + 1)))
+        for name, init in (("device", "random"), ("device_greedy", "greedy")):
+            final, feas, trace, secs = device_runs(inst, seeds, a.pop, dg, a.steps, a.device_children,
+                                                   a.device_schedule, init=init)
+            res["runs"][name] = summarize(final, feas, trace, cps)
+            res["runs"][name]["seconds_per_run"] = secs
+        vp, vg = (np.array(res["runs"][n]["final_log_value"]) for n in ("device", "device_greedy"))
+        same = bool(np.array_equal(vp, vg))
+        res["tests"] = {"greedy_vs_random": {
+            "final_value_mannwhitney_p": 1.0 if same else float(stats.mannwhitneyu(vg, vp, alternative="two-sided").pvalue),
+            "median_greedy": float(np.median(vg)), "median_random": float(np.median(vp))}}
         print(json.dumps(res), flush=True)
         if a.out:
             pathlib.Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
