@@ -29,8 +29,10 @@
  * event and fit up to roughly 12,000 events.
  *
  * Additions with no counterpart in the reference have headers of their own:
- * ttga_report.h, ttga_unique.h and ttga_greedy.h (a greedy constructive
- * initial population, the counterpart of tt_random_init).
+ * ttga_report.h, ttga_unique.h, ttga_greedy.h (a greedy constructive
+ * initial population, the counterpart of tt_random_init) and ttga_kempe.h
+ * (the Kempe-chain interchange, a move of a whole conflict component
+ * between two timeslots).
  */
 #ifndef TTGA_H
 #define TTGA_H
@@ -222,7 +224,9 @@ int tt_ga_replace(const tt_problem* p, uint8_t* pop_slot, uint8_t* pop_room, int
  *   bit 4 (16) the local search's per-stream redo list overflowed (unreachable:
  *              it holds P entries and a launch lists each wave at most once);
  *              the individuals not listed are left unsearched;
- *   bit 5 (32) ttga_greedy.h's tt_greedy_init skipped an order entry outside 0..E-1.
+ *   bit 5 (32) ttga_greedy.h's tt_greedy_init skipped an order entry outside 0..E-1;
+ *   bit 6 (64) ttga_kempe.h's tt_kempe_move left a row with a slot gene >= 45 or
+ *              a room gene >= R untouched.
  * Synchronises the device. */
 int tt_device_status(const tt_problem* p, int32_t* status);
 

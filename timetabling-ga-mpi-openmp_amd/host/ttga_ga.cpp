@@ -11,7 +11,14 @@
 //
 //   ttga-ga -i instance.tim [-s seed] [-p type] [-c children]
 //           [-p1 x -p2 y -p3 z] [--gpus G] [--islands K] [--pop N] [--generations n] [--rccl] [--stagger]
-//           [--report] [--unique] [--init random|greedy]
+//           [--report] [--unique] [--init random|greedy] [--kempe P] [--kempe-max-chain N]
+//
+// --kempe P: every child gets tt_kempe_move (include/ttga_kempe.h) with
+// probability P directly after tt_ga_breed and before its search, on its own
+// stream; --kempe-max-chain N refuses chains of more than N events (0, the
+// default: no cap). Each island then prints one
+// {"kempe": {"children", "meanChain", "moved", "rejected"}} line after its
+// solution line (ttga.islands prints the same). The default is 0: no call.
 //
 // --init greedy: the initial population is built by tt_greedy_init
 // (include/ttga_greedy.h) instead of RandomInitialSolution (ga.cpp:431); the
@@ -74,6 +81,7 @@
 
 #include "../../include/ttga_report.h"
 #include "../../include/ttga_greedy.h"
+#include "../../include/ttga_kempe.h"
 #include "../../include/ttga_unique.h"
 
 namespace {
@@ -109,6 +117,8 @@ struct Control {
     bool report = false;                          // a population report line per island
     bool unique = false;                          // duplicate-free replacement, a unique line per island
     bool greedy = false;                          // --init greedy: tt_greedy_init builds the initial population
+    double kempe = 0.0;                           // --kempe: tt_kempe_move's probability (0: never called)
+    int kempe_max_chain = 0;                      // --kempe-max-chain (0: no cap)
 };
 
 // Control::Control (Control.cpp:3-137) plus the --gpus/--pop/--generations extensions.
@@ -137,6 +147,22 @@ Control parse_control(int argc, char** argv) {
             std::exit(1);
         }
         c.greedy = *(it + 1) == "greedy";
+        args.erase(it, it + 2);
+    }
+    for (const char* k : {"--kempe", "--kempe-max-chain"}) {
+        auto it = std::find(args.begin(), args.end(), k);
+        if (it == args.end()) continue;
+        char* end = nullptr;
+        const bool prob = !std::strcmp(k, "--kempe");
+        const double v = it + 1 == args.end() ? -1.0 : std::strtod((it + 1)->c_str(), &end);
+        // an integer for the cap; a NaN fails both comparisons
+        if (!(v >= 0 && (prob ? v <= 1 : v == std::floor(v) && v <= INT_MAX)) || !end || *end) {
+            std::cerr << "Error: --kempe must be a probability in [0, 1], --kempe-max-chain an integer >= 0"
+                      << std::endl;
+            std::exit(1);
+        }
+        if (prob) c.kempe = v;
+        else c.kempe_max_chain = (int)v;
         args.erase(it, it + 2);
     }
     for (const char* k : {"--gpus", "--islands", "--pop", "--generations", "--children", "--stagger-parts"}) {
@@ -522,6 +548,13 @@ struct Island {
     uint8_t* keep = nullptr;                          // [C], part j's flags at keep + off
     int32_t* kept_log = nullptr;
     long kept_cap = 0, kept_used = 0, children = 0;
+    // --kempe: tt_kempe_move on every sub-batch between its breed and its search; each
+    // call leaves its chain lengths in the next n entries of chain_log on the device,
+    // read once at the end, so no generation waits for them
+    double kempe = 0.0;
+    int kempe_max_chain = 0;
+    int32_t* chain_log = nullptr;
+    long chain_cap = 0, chain_used = 0;
 
     size_t work_bytes(int n) const {
         return std::max<size_t>(unique ? tt_ga_unique_work_bytes(N, n, E) : tt_ga_work_bytes(N, E), 16);
@@ -549,6 +582,10 @@ struct Island {
             check_hip(hipMalloc(&keep, (size_t)C), "hipMalloc");
             check_hip(hipMalloc(&kept_log, 4 * (size_t)kept_cap), "hipMalloc");
             check_hip(hipMemset(kept_log, 0, 4 * (size_t)kept_cap), "hipMemset");
+        }
+        if (kempe > 0) {
+            chain_cap = std::max(replacements / parts * C, 1L);        // generations x children
+            check_hip(hipMalloc(&chain_log, 4 * (size_t)chain_cap), "hipMalloc");
         }
         migrant_bytes = 2 * (size_t)E + 13;
         check_hip(hipMalloc(&send_best, migrant_bytes), "hipMalloc");
@@ -633,6 +670,37 @@ struct Island {
                  "tt_ga_breed");
     }
 
+    // --kempe: the Kempe-chain move on rows [off, off + n) on s, from the children's own streams
+    void kempe_move(int off, int n, hipStream_t s) {
+        Pop c = child_rows(off, n);
+        if (chain_used + n > chain_cap) die("more Kempe moves than planned for");
+        check_tt(tt_kempe_move(tp, c.slot, c.room, rng_child + off, n, kempe, kempe_max_chain, chain_log + chain_used,
+                               s),
+                 "tt_kempe_move");
+        chain_used += n;
+    }
+
+    // the --kempe line: every call's chain lengths in one copy (ttga/ga.py kempe_line)
+    Json kempe_report() {
+        flush();
+        std::vector<int32_t> len(chain_used);
+        for (const Part& p : part) check_hip(hipStreamSynchronize(p.s), "hipStreamSynchronize");
+        if (!len.empty())
+            check_hip(hipMemcpy(len.data(), chain_log, 4 * len.size(), hipMemcpyDeviceToHost), "hipMemcpy");
+        long moved = 0, rejected = 0, events = 0;
+        for (int32_t v : len) {
+            moved += v > 0;
+            rejected += v < 0;
+            if (v > 0) events += v;
+        }
+        Json k;
+        k.obj["children"] = Json::I(chain_used);
+        k.obj["moved"] = Json::I(moved);
+        k.obj["rejected"] = Json::I(rejected);
+        k.obj["meanChain"] = Json::D(moved ? (double)events / (double)moved : 0.0);
+        return wrap("kempe", k);
+    }
+
     // LPT order (C >= kLptMinChildren), localSearch and evaluation of rows [off, off + n) on s
     // (the search and the evaluation in one launch: ga.cpp:574-575)
     void search(int off, int n, hipStream_t s, void* w) {
@@ -702,6 +770,7 @@ struct Island {
         breed(p.off, p.n, p.s);
         wrote_population(p.s);
         if (!pending.empty() && (int)pending.size() >= parts - 1) replace_oldest();   // replace(h - parts + 1) after breed(h)
+        if (kempe > 0) kempe_move(p.off, p.n, p.s);
         search(p.off, p.n, p.s, p.work);
         pending.push_back(j);
         if ((int)pending.size() >= parts) replace_oldest();
@@ -815,7 +884,7 @@ struct Island {
         pop.release();
         child.release();
         for (void* p : {(void*)rng_init, (void*)rng_child, (void*)flags, (void*)order, (void*)send_best,
-                        (void*)send_second, (void*)recv_buf, (void*)keep, (void*)kept_log})
+                        (void*)send_second, (void*)recv_buf, (void*)keep, (void*)kept_log, (void*)chain_log})
             if (p) (void)hipFree(p);
         for (size_t j = 0; j < part.size(); j++) {
             if (part[j].work) (void)hipFree(part[j].work);
@@ -875,6 +944,8 @@ int main(int argc, char** argv) {
         I.parts = ctl.stagger >= 2 ? std::min(ctl.stagger, C) : 1;
         I.unique = ctl.unique;
         I.greedy = ctl.greedy;
+        I.kempe = ctl.kempe;
+        I.kempe_max_chain = ctl.kempe_max_chain;
     }
     std::vector<ncclComm_t> comms(K, nullptr);
     if (rccl) {
@@ -995,6 +1066,7 @@ int main(int argc, char** argv) {
         check_hip(hipMemcpy(sl.data(), I.pop.slot, I.E, hipMemcpyDeviceToHost), "hipMemcpy");
         check_hip(hipMemcpy(rm.data(), I.pop.room, I.E, hipMemcpyDeviceToHost), "hipMemcpy");
         out.line(solution_line(b.feasible, b.scv, b.hcv, sl, rm, k, seconds_since(t_begin)));
+        if (ctl.kempe > 0) out.line(I.kempe_report());
     }
     if (ctl.unique)
         for (int k = 0; k < K; k++) {

@@ -201,12 +201,19 @@ class Island(Members):
     population whose genomes are pairwise distinct stays so, migrants aside:
     migration is unchanged and a migrant may duplicate a member of its
     destination. unique_stats() reports the children bred and dropped.
+
+    kempe=p > 0: every sub-batch's children get tt_kempe_move
+    (include/ttga_kempe.h) with probability p, at most kempe_max_chain events
+    a chain (0: no cap), on the sub-batch's stream directly after tt_ga_breed
+    and before the search, drawing from the children's own streams. kempe=0
+    issues no call at all. kempe_stats() reports what the moves did.
     """
 
     def __init__(self, dp, pop_size: int = 10, children: int = 1, max_steps: int = 200, seed: int = 1,
                  p_cross: float = 0.8, p_mut: float = 0.5, skip_init_draws: bool = True, device=None,
                  p1: float = 1.0, p2: float = 1.0, p3: float = 0.0, lpt: bool | None = None, stream=None,
-                 schedule: str = "batch", parts: int = 2, unique: bool = False, init: str = "random"):
+                 schedule: str = "batch", parts: int = 2, unique: bool = False, init: str = "random",
+                 kempe: float = 0.0, kempe_max_chain: int = 0):
         """stream: a torch.cuda.Stream of the island's own, or None (torch's current
         stream). Islands multiplexed on one GPU (ttga.islands --islands K) each take
         one, so one island's launches fill the SIMD slots another's local-search tail
@@ -216,6 +223,10 @@ class Island(Members):
         import torch
         if init not in ("random", "greedy"):
             raise ValueError("init must be 'random' or 'greedy'")
+        if not (0.0 <= float(kempe) <= 1.0):
+            raise ValueError("kempe must be a probability in [0, 1]")
+        if int(kempe_max_chain) < 0:
+            raise ValueError("kempe_max_chain must be >= 0 (0: no cap)")
         if not (1 <= children <= pop_size):
             raise ValueError("need 1 <= children <= pop_size")
         if schedule not in ("batch", "staggered"):
@@ -237,6 +248,7 @@ class Island(Members):
         self.rng_child = torch.from_numpy(stream_seeds(seed, self.N, self.C)).to(dev)
         self.unique = bool(unique)
         self.init = init
+        self.kempe, self.kempe_max_chain = float(kempe), int(kempe_max_chain)
         self.generation = 0
         self.schedule = schedule
         self.parts = int(parts) if schedule == "staggered" else 1
@@ -272,6 +284,14 @@ class Island(Members):
             self._init_kept = torch.zeros(1, dtype=torch.int32, device=dev)
             self._dropped = torch.zeros(1, dtype=torch.int64, device=dev)
             self._extra += [self._init_kept, self._dropped]
+        # kempe: each part's chain lengths and its running (moved, rejected, events moved),
+        # added up on the part's stream behind the move; the children moved on, on the host
+        if self.kempe > 0:
+            for p in self._parts:
+                p.chain = torch.zeros(p.n, dtype=torch.int32, device=dev)
+                p.kempe_sums = torch.zeros(3, dtype=torch.int64, device=dev)
+                self._extra += [p.chain, p.kempe_sums]
+        self._kempe_children = 0
         self._replaced = 0
         self._pending = []                            # parts searched but not yet replaced, in breed order
         self._last_replace = 0                        # part whose work buffer holds the last replace's source
@@ -430,10 +450,32 @@ class Island(Members):
             self._record_op(p.stream)
             if self._pending and len(self._pending) >= self.parts - 1:
                 self._replace_oldest()                                      # replace(h - parts + 1) after breed(h)
+            if self.kempe > 0:
+                self._kempe(p)
             self._search(p.child, p.rng, p.work)
             self._pending.append(j)
             if len(self._pending) >= self.parts:
                 self._replace_oldest()
+
+    def _kempe(self, p):
+        """tt_kempe_move on the children of part p (on its stream, the current
+        one) and its counts, summed on the device behind the move."""
+        import torch
+        self.dp.kempe_move(p.child["slot"], p.child["room"], p.rng, self.kempe, self.kempe_max_chain, p.chain)
+        p.kempe_sums += torch.stack([(p.chain > 0).sum(), (p.chain < 0).sum(), p.chain.clamp(min=0).sum()])
+        self._kempe_children += p.n
+
+    def kempe_stats(self) -> dict:
+        """Island(kempe > 0): the children tt_kempe_move was called on, how many
+        of them moved a chain, how many chains the cap rejected, and the events
+        moved in all, as Python ints. Pending sub-batches are replaced first;
+        synchronises."""
+        if not self.kempe > 0:
+            raise ValueError("kempe_stats() needs Island(kempe > 0)")
+        self.flush()
+        self.sync()
+        moved, rejected, events = (int(v) for v in sum(p.kempe_sums.cpu() for p in self._parts).tolist())
+        return {"children": int(self._kempe_children), "moved": moved, "rejected": rejected, "chain_events": events}
 
     def _replace_oldest(self):
         j = self._pending.pop(0)
@@ -616,6 +658,15 @@ def unique_line(stats: dict, proc_id: int, island: int) -> str:
     the island's global id (procID) and its index within the process."""
     return json_line({"unique": {"children": int(stats["children"]), "distinct": int(stats["distinct"]),
                                  "dropped": int(stats["dropped"]), "island": int(island), "procID": int(proc_id)}})
+
+
+def kempe_line(stats: dict) -> str:
+    """The drivers' --kempe line of one island: Island.kempe_stats() with the
+    mean length of the chains moved (0 when none moved)."""
+    moved = int(stats["moved"])
+    return json_line({"kempe": {"children": int(stats["children"]), "moved": moved,
+                                "rejected": int(stats["rejected"]),
+                                "meanChain": float(stats["chain_events"]) / moved if moved else 0.0}})
 
 
 def run_final_line(procs: int, threads: int, total_time: float) -> str:

@@ -23,6 +23,11 @@ Reference correspondence:
   `--init random|greedy` (greedy: the initial population is built by
   tt_greedy_init, include/ttga_greedy.h, instead of RandomInitialSolution;
   the default is random),
+  `--kempe P` / `--kempe-max-chain N` (every child gets tt_kempe_move,
+  include/ttga_kempe.h, with probability P after breeding and before its
+  search, chains of more than N events refused, 0 = no cap; each island then
+  prints a `kempe` line after its solution line: children, chains moved,
+  chains refused, mean length of the chains moved),
   `--stagger` / `--stagger-parts P` (the children of a generation as 2 / P
   sub-batches on as many streams, each bred P - 1 sub-batches behind:
   ttga.ga.Island's staggered schedule),
@@ -83,6 +88,18 @@ def parse_control(argv, out=sys.stdout, err=sys.stderr) -> dict:
             raise SystemExit(1)
         extra["init"] = args[i + 1]
         del args[i:i + 2]
+    for k, conv in (("--kempe", float), ("--kempe-max-chain", int)):     # include/ttga_kempe.h
+        if k in args:
+            i = args.index(k)
+            try:
+                v = conv(args[i + 1])
+            except (IndexError, ValueError):
+                v = -1
+            if not (v >= 0 and (conv is int or v <= 1)):     # a NaN fails both
+                err.write("Error: --kempe must be a probability in [0, 1], --kempe-max-chain an integer >= 0\n")
+                raise SystemExit(1)
+            extra[k[2:].replace("-", "_")] = v
+            del args[i:i + 2]
     if len(args) % 2 != 0:
         err.write("Parse error: Number of command line parameters incorrect\nUsage:\n" + USAGE + "\n")
         raise SystemExit(1)
@@ -224,7 +241,8 @@ def main(argv=None):
     import torch.distributed as dist
 
     from . import instance as tim
-    from .ga import CostLog, Island, max_steps_for, run_best_line, run_final_line, solution_line, unique_line
+    from .ga import (CostLog, Island, kempe_line, max_steps_for, run_best_line, run_final_line, solution_line,
+                     unique_line)
 
     from .native import DeviceProblem
 
@@ -276,7 +294,8 @@ def main(argv=None):
     islands = [Island(dp, pop_size=N, children=C, max_steps=max_steps_for(ctl["problem_type"]),
                       seed=rank_seed(seed, rank * K + k), p1=ctl["p1"], p2=ctl["p2"], p3=ctl["p3"],
                       stream=streams[k], schedule="staggered" if parts >= 2 else "batch", parts=max(parts, 2),
-                      unique=bool(ctl.get("unique")), init=ctl.get("init", "random"))
+                      unique=bool(ctl.get("unique")), init=ctl.get("init", "random"),
+                      kempe=ctl.get("kempe", 0.0), kempe_max_chain=ctl.get("kempe_max_chain", 0))
                for k in range(K)]
     if rank == 0:
         islands[0].initialize()
@@ -322,6 +341,8 @@ def main(argv=None):
         out.write(run_best_line(vals[0][0], gmin) + "\n")
     for k, isl in enumerate(islands):
         out.write(solution_line(isl.member(0), rank * K + k, time.perf_counter() - t_begin) + "\n")
+        if ctl.get("kempe", 0.0) > 0:
+            out.write(kempe_line(isl.kempe_stats()) + "\n")
     if ctl.get("unique"):
         for k, isl in enumerate(islands):
             out.write(unique_line(isl.unique_stats(), rank * K + k, k) + "\n")

@@ -37,6 +37,9 @@ UNIQUE_EXPORTS = ("tt_genome_work_bytes", "tt_genome_first", "tt_ga_unique_work_
 # include/ttga_greedy.h
 GREEDY_EXPORTS = ("tt_greedy_work_bytes", "tt_greedy_order", "tt_greedy_init")
 
+# include/ttga_kempe.h
+KEMPE_EXPORTS = ("tt_kempe_move",)
+
 _lib = None
 
 
@@ -102,6 +105,8 @@ def load(path: os.PathLike | str | None = None) -> ctypes.CDLL:
     lib.tt_greedy_order.restype = ctypes.c_int
     lib.tt_greedy_init.argtypes = [vp, vp, vp, vp, vp, i32, vp]
     lib.tt_greedy_init.restype = ctypes.c_int
+    lib.tt_kempe_move.argtypes = [vp, vp, vp, vp, i32, dbl, i32, vp, vp]
+    lib.tt_kempe_move.restype = ctypes.c_int
     for name in EXPORTS:
         if name not in ("tt_last_error", "tt_ga_work_bytes", "tt_ga_work_source_offset"):
             getattr(lib, name).restype = ctypes.c_int
@@ -428,6 +433,24 @@ class DeviceProblem:
             raise ValueError("order must be a contiguous int32 CUDA tensor of E entries on the population's device")
         _check(self.lib, self.lib.tt_greedy_init(self.handle, order.data_ptr(), rng.data_ptr(), slot.data_ptr(),
                                                  room.data_ptr(), P, self._stream(slot)))
+
+    # -- Kempe-chain interchange (include/ttga_kempe.h) ------------------------------
+    def kempe_move(self, slot, room, rng, prob, max_chain=0, chain_len=None):
+        """tt_kempe_move in place on slot/room [P, E] with the streams rng [P]:
+        with probability `prob` an individual moves the conflict component of
+        one event between two timeslots (at most max_chain events; 0: no cap).
+        chain_len: optional int32 [P] CUDA tensor (events moved, minus the
+        component's size where the cap refused it, 0 where nothing was tried)."""
+        import torch
+        P = self._pop(slot, room)
+        self._rng(rng, P)
+        if chain_len is not None and not (chain_len.is_cuda and chain_len.dtype == torch.int32
+                                          and chain_len.is_contiguous() and chain_len.numel() == P
+                                          and chain_len.device == slot.device):
+            raise ValueError("chain_len must be a contiguous int32 CUDA tensor of P entries on the population's device")
+        _check(self.lib, self.lib.tt_kempe_move(
+            self.handle, slot.data_ptr(), room.data_ptr(), rng.data_ptr(), P, float(prob), int(max_chain),
+            ctypes.c_void_p(chain_len.data_ptr() if chain_len is not None else None), self._stream(slot)))
 
     @staticmethod
     def _rng(rng, P):

@@ -25,7 +25,7 @@ slots, rooms, hcv, scv, feasible, penalty and final RNG states
     python tools/bench_ga.py [--config comp01] [--pop 65536] [--children 65536]
                              [--gens 3] [--steps 200] [--cpu-sample 512]
                              [--warm-gens N] [--warm-feasible F] [--unique]
-                             [--init random|greedy]
+                             [--init random|greedy] [--kempe P] [--kempe-max-chain N]
 
 --warm-gens / --warm-feasible run untimed generations first, until a fraction F
 of the population is feasible (or N generations), so the timed generations
@@ -37,6 +37,11 @@ run's at the first dropped child, so the two runs' times are not like for like.
 --init greedy builds the initial population with tt_greedy_init
 (include/ttga_greedy.h, Island(init="greedy")) instead of tt_random_init; the
 record then carries "init" and the feasible share right after initialize().
+--kempe P runs Island(kempe=P, kempe_max_chain=N): every child gets tt_kempe_move
+(include/ttga_kempe.h) between breeding and its search; the record then carries
+"kempe" (the probability, the cap, the children, the chains moved and rejected
+and their mean length). Its populations part from the plain run's at the first
+chain moved, so the two runs' times are not like for like.
 """
 import argparse
 import json
@@ -90,6 +95,9 @@ def parser():
     ap.add_argument("--unique", action="store_true", help="duplicate-free replacement (Island(unique=True))")
     ap.add_argument("--init", choices=["random", "greedy"], default="random",
                     help="the initial population: tt_random_init or tt_greedy_init (Island(init=...))")
+    ap.add_argument("--kempe", type=float, default=0.0,
+                    help="probability of tt_kempe_move per child (Island(kempe=...)); 0: never called")
+    ap.add_argument("--kempe-max-chain", type=int, default=0, help="the cap on a chain's length (0: none)")
     return ap
 
 
@@ -102,7 +110,8 @@ def run_ga(a):
     seeds = [a.seed] + [rank_seed(a.seed, k) for k in range(1, K)]
     isls = [Island(dp, pop_size=a.pop, children=a.children, max_steps=a.steps, seed=seeds[k],
                    lpt=None if a.lpt == "auto" else a.lpt == "on", stream=torch.cuda.Stream() if K > 1 else None,
-                   schedule=a.schedule, parts=a.parts, unique=a.unique, init=a.init)
+                   schedule=a.schedule, parts=a.parts, unique=a.unique, init=a.init, kempe=a.kempe,
+                   kempe_max_chain=a.kempe_max_chain)
             for k in range(K)]
     isl = isls[0]
     torch.cuda.synchronize()
@@ -172,8 +181,14 @@ def run_ga(a):
         stats = [i.unique_stats() for i in isls]
         out["unique"] = {k: sum(s[k] for s in stats) for k in ("children", "dropped", "distinct")}
         out["unique"]["dropped_share"] = out["unique"]["dropped"] / max(1, out["unique"]["children"])
+    if a.kempe > 0:
+        stats = [i.kempe_stats() for i in isls]
+        k = {key: sum(s[key] for s in stats) for key in ("children", "moved", "rejected", "chain_events")}
+        out["kempe"] = {"prob": a.kempe, "max_chain": a.kempe_max_chain, "children": k["children"],
+                        "moved": k["moved"], "rejected": k["rejected"],
+                        "mean_chain": k["chain_events"] / k["moved"] if k["moved"] else 0.0}
     R = ref()
-    if R is not None and a.cpu_sample > 0:
+    if R is not None and a.cpu_sample > 0 and not a.kempe > 0:
         n = min(a.cpu_sample, a.children)
         threads, total, model = host_cores()
         h = R.problem(inst)

@@ -29,6 +29,13 @@ medians, the children dropped and the distinct genomes left per run.
 (tt_greedy_init, include/ttga_greedy.h) against the plain island, same seeds
 and parameters, no reference run: final values (Mann-Whitney U, two-sided),
 their medians, and the medians of the logged best at generation checkpoints.
+
+--kempe P [--kempe-max-chain N] does the same for the Kempe-chain move:
+Island(kempe=P, kempe_max_chain=N) (tt_kempe_move, include/ttga_kempe.h) against
+the plain island, same seeds and parameters, no reference run: final values
+(Mann-Whitney U, two-sided), their medians, the medians of the logged best at
+generation checkpoints, and per run the chains moved, rejected and their mean
+length.
 """
 import argparse
 import json
@@ -58,7 +65,7 @@ def summarize(final, feas, trace, checkpoints):
 
 
 def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch", unique=False, stats_out=None,
-                init="random"):
+                init="random", kempe=0.0, kempe_max_chain=0):
     import torch
 
     from ttga import native
@@ -70,7 +77,7 @@ def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch", uni
     secs = []
     for k, s in enumerate(seeds):
         isl = Island(dp, pop_size=pop, children=children, max_steps=steps, seed=int(s), schedule=schedule,
-                     unique=unique, init=init)
+                     unique=unique, init=init, kempe=kempe, kempe_max_chain=kempe_max_chain)
         tr = torch.zeros(gens + 1, dtype=torch.int64, device="cuda")
         p = isl.pop
 
@@ -93,7 +100,9 @@ def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch", uni
         feas[k] = 1 if isl.member_meta(0)[0] else 0
         final[k] = trace[k, -1]
         if stats_out is not None:
-            if unique:
+            if kempe > 0:
+                stats_out.append(isl.kempe_stats())
+            elif unique:
                 stats_out.append(isl.unique_stats())
             else:            # the plain island's distinct genomes, for the comparison
                 first = dp.genome_first(isl.pop["slot"], isl.pop["room"])
@@ -119,6 +128,9 @@ def main():
                     help="compare Island(unique=True) with the plain island (no reference run)")
     ap.add_argument("--init", choices=["random", "greedy"], default="random",
                     help="greedy: compare Island(init='greedy') with the plain island (no reference run)")
+    ap.add_argument("--kempe", type=float, default=0.0,
+                    help="P > 0: compare Island(kempe=P) with the plain island (no reference run)")
+    ap.add_argument("--kempe-max-chain", type=int, default=0, help="the cap on a chain's length (0: none)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     from scipy import stats
@@ -176,6 +188,31 @@ def main():
         res["tests"] = {"greedy_vs_random": {
             "final_value_mannwhitney_p": 1.0 if same else float(stats.mannwhitneyu(vg, vp, alternative="two-sided").pvalue),
             "median_greedy": float(np.median(vg)), "median_random": float(np.median(vp))}}
+        print(json.dumps(res), flush=True)
+        if a.out:
+            pathlib.Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
+        return
+    if a.kempe > 0:
+        dg = a.device_gens or a.gens
+        res["children_per_generation"], res["generations"] = a.device_children, dg
+        res["kempe"], res["kempe_max_chain"] = a.kempe, a.kempe_max_chain
+        cps = sorted({0, 1, 10, 100, dg // 2, dg} & set(range(dg + 1)))
+        for name, prob in (("device", 0.0), ("device_kempe", a.kempe)):
+            st = [] if prob > 0 else None
+            final, feas, trace, secs = device_runs(inst, seeds, a.pop, dg, a.steps, a.device_children,
+                                                   a.device_schedule, stats_out=st, kempe=prob,
+                                                   kempe_max_chain=a.kempe_max_chain)
+            res["runs"][name] = summarize(final, feas, trace, cps)
+            res["runs"][name]["seconds_per_run"] = secs
+            if st:
+                res["runs"][name]["kempe_stats"] = st
+                moved, events = sum(s["moved"] for s in st), sum(s["chain_events"] for s in st)
+                res["runs"][name]["mean_chain"] = events / moved if moved else 0.0
+        vp, vk = (np.array(res["runs"][n]["final_log_value"]) for n in ("device", "device_kempe"))
+        same = bool(np.array_equal(vp, vk))
+        res["tests"] = {"kempe_vs_plain": {
+            "final_value_mannwhitney_p": 1.0 if same else float(stats.mannwhitneyu(vk, vp, alternative="two-sided").pvalue),
+            "median_kempe": float(np.median(vk)), "median_plain": float(np.median(vp))}}
         print(json.dumps(res), flush=True)
         if a.out:
             pathlib.Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
