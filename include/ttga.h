@@ -30,9 +30,10 @@
  *
  * Additions with no counterpart in the reference have headers of their own:
  * ttga_report.h, ttga_unique.h, ttga_greedy.h (a greedy constructive
- * initial population, the counterpart of tt_random_init) and ttga_kempe.h
+ * initial population, the counterpart of tt_random_init), ttga_kempe.h
  * (the Kempe-chain interchange, a move of a whole conflict component
- * between two timeslots).
+ * between two timeslots) and ttga_slotswap.h (the timeslot-swap descent:
+ * two whole timeslots trade their events while that lowers scv).
  */
 #ifndef TTGA_H
 #define TTGA_H
@@ -226,7 +227,9 @@ int tt_ga_replace(const tt_problem* p, uint8_t* pop_slot, uint8_t* pop_room, int
  *              the individuals not listed are left unsearched;
  *   bit 5 (32) ttga_greedy.h's tt_greedy_init skipped an order entry outside 0..E-1;
  *   bit 6 (64) ttga_kempe.h's tt_kempe_move left a row with a slot gene >= 45 or
- *              a room gene >= R untouched.
+ *              a room gene >= R untouched;
+ *   bit 7 (128) ttga_slotswap.h's tt_slot_swap left a row with a slot gene >= 45
+ *              untouched.
  * Synchronises the device. */
 int tt_device_status(const tt_problem* p, int32_t* status);
 

@@ -12,6 +12,15 @@
 //   ttga-ga -i instance.tim [-s seed] [-p type] [-c children]
 //           [-p1 x -p2 y -p3 z] [--gpus G] [--islands K] [--pop N] [--generations n] [--rccl] [--stagger]
 //           [--report] [--unique] [--init random|greedy] [--kempe P] [--kempe-max-chain N]
+//           [--slot-swap N]
+//
+// --slot-swap N: tt_slot_swap (include/ttga_slotswap.h) with max_passes N runs
+// directly behind every tt_local_search_eval, on the same stream, and lowers
+// the searched rows' scv and penalty in place: on every sub-batch of children
+// before its replacement, on the members before the initial sort. Each island
+// then prints one {"slotSwap": {"gain", "improved", "meanPasses", "rows"}} line
+// after the solution, kempe and unique lines (ttga.islands prints the same).
+// The default is 0: no call.
 //
 // --kempe P: every child gets tt_kempe_move (include/ttga_kempe.h) with
 // probability P directly after tt_ga_breed and before its search, on its own
@@ -82,6 +91,7 @@
 #include "../../include/ttga_report.h"
 #include "../../include/ttga_greedy.h"
 #include "../../include/ttga_kempe.h"
+#include "../../include/ttga_slotswap.h"
 #include "../../include/ttga_unique.h"
 
 namespace {
@@ -119,6 +129,7 @@ struct Control {
     bool greedy = false;                          // --init greedy: tt_greedy_init builds the initial population
     double kempe = 0.0;                           // --kempe: tt_kempe_move's probability (0: never called)
     int kempe_max_chain = 0;                      // --kempe-max-chain (0: no cap)
+    int slot_swap = 0;                            // --slot-swap: tt_slot_swap's max_passes (0: never called)
 };
 
 // Control::Control (Control.cpp:3-137) plus the --gpus/--pop/--generations extensions.
@@ -163,6 +174,16 @@ Control parse_control(int argc, char** argv) {
         }
         if (prob) c.kempe = v;
         else c.kempe_max_chain = (int)v;
+        args.erase(it, it + 2);
+    }
+    if (auto it = std::find(args.begin(), args.end(), "--slot-swap"); it != args.end()) {
+        char* end = nullptr;
+        const double v = it + 1 == args.end() ? -1.0 : std::strtod((it + 1)->c_str(), &end);
+        if (!(v >= 0 && v == std::floor(v) && v <= INT_MAX) || !end || *end || (it + 1)->empty()) {
+            std::cerr << "Error: --slot-swap must be a non-negative integer" << std::endl;
+            std::exit(1);
+        }
+        c.slot_swap = (int)v;
         args.erase(it, it + 2);
     }
     for (const char* k : {"--gpus", "--islands", "--pop", "--generations", "--children", "--stagger-parts"}) {
@@ -555,6 +576,12 @@ struct Island {
     int kempe_max_chain = 0;
     int32_t* chain_log = nullptr;
     long chain_cap = 0, chain_used = 0;
+    // --slot-swap: tt_slot_swap behind every search; each call leaves its gains in the next
+    // n entries of swap_log and its passes in the n entries swap_cap further on, read once
+    // at the end, so no generation waits for them
+    int slot_swap = 0;
+    int32_t* swap_log = nullptr;
+    long swap_cap = 0, swap_used = 0;
 
     size_t work_bytes(int n) const {
         return std::max<size_t>(unique ? tt_ga_unique_work_bytes(N, n, E) : tt_ga_work_bytes(N, E), 16);
@@ -586,6 +613,10 @@ struct Island {
         if (kempe > 0) {
             chain_cap = std::max(replacements / parts * C, 1L);        // generations x children
             check_hip(hipMalloc(&chain_log, 4 * (size_t)chain_cap), "hipMalloc");
+        }
+        if (slot_swap > 0) {
+            swap_cap = N + std::max(replacements / parts * C, 1L);     // the members + generations x children
+            check_hip(hipMalloc(&swap_log, 2 * 4 * (size_t)swap_cap), "hipMalloc");
         }
         migrant_bytes = 2 * (size_t)E + 13;
         check_hip(hipMalloc(&send_best, migrant_bytes), "hipMalloc");
@@ -640,6 +671,7 @@ struct Island {
         check_tt(tt_local_search_eval(tp, pop.slot, pop.room, rng_init, N, max_steps, p1, p2, p3, nullptr, pop.hcv,
                                       pop.scv, pop.feasible, pop.penalty, st),
                  "tt_local_search_eval");
+        if (slot_swap > 0) swap_slots(pop, st);
         if (unique)
             check_tt(tt_ga_replace_unique(tp, pop.slot, pop.room, pop.hcv, pop.scv, pop.feasible, pop.penalty, N,
                                           pop.slot, pop.room, pop.hcv, pop.scv, pop.feasible, pop.penalty, 0, nullptr,
@@ -699,6 +731,40 @@ struct Island {
         k.obj["rejected"] = Json::I(rejected);
         k.obj["meanChain"] = Json::D(moved ? (double)events / (double)moved : 0.0);
         return wrap("kempe", k);
+    }
+
+    // --slot-swap: the timeslot-swap descent on the searched rows r on s, behind their search
+    // and evaluation; their scv and penalty are lowered in place
+    void swap_slots(const Pop& r, hipStream_t s) {
+        if (swap_used + r.n > swap_cap) die("more timeslot-swap rows than planned for");
+        check_tt(tt_slot_swap(tp, r.slot, r.n, slot_swap, r.scv, r.penalty, swap_log + swap_used,
+                              swap_log + swap_cap + swap_used, nullptr, s),
+                 "tt_slot_swap");
+        swap_used += r.n;
+    }
+
+    // the --slot-swap line: every call's gains and passes in two copies (ttga/ga.py slot_swap_line)
+    Json slot_swap_report() {
+        flush();
+        std::vector<int32_t> gain(swap_used), pass(swap_used);
+        for (const Part& p : part) check_hip(hipStreamSynchronize(p.s), "hipStreamSynchronize");
+        check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
+        if (swap_used) {
+            check_hip(hipMemcpy(gain.data(), swap_log, 4 * gain.size(), hipMemcpyDeviceToHost), "hipMemcpy");
+            check_hip(hipMemcpy(pass.data(), swap_log + swap_cap, 4 * pass.size(), hipMemcpyDeviceToHost), "hipMemcpy");
+        }
+        long improved = 0, passes = 0, total = 0;
+        for (long i = 0; i < swap_used; i++) {
+            improved += pass[i] > 0;
+            passes += pass[i];
+            total += gain[i];
+        }
+        Json k;
+        k.obj["rows"] = Json::I(swap_used);
+        k.obj["improved"] = Json::I(improved);
+        k.obj["gain"] = Json::I(total);
+        k.obj["meanPasses"] = Json::D(improved ? (double)passes / (double)improved : 0.0);
+        return wrap("slotSwap", k);
     }
 
     // LPT order (C >= kLptMinChildren), localSearch and evaluation of rows [off, off + n) on s
@@ -772,6 +838,7 @@ struct Island {
         if (!pending.empty() && (int)pending.size() >= parts - 1) replace_oldest();   // replace(h - parts + 1) after breed(h)
         if (kempe > 0) kempe_move(p.off, p.n, p.s);
         search(p.off, p.n, p.s, p.work);
+        if (slot_swap > 0) swap_slots(child_rows(p.off, p.n), p.s);
         pending.push_back(j);
         if ((int)pending.size() >= parts) replace_oldest();
     }
@@ -884,7 +951,8 @@ struct Island {
         pop.release();
         child.release();
         for (void* p : {(void*)rng_init, (void*)rng_child, (void*)flags, (void*)order, (void*)send_best,
-                        (void*)send_second, (void*)recv_buf, (void*)keep, (void*)kept_log, (void*)chain_log})
+                        (void*)send_second, (void*)recv_buf, (void*)keep, (void*)kept_log, (void*)chain_log,
+                        (void*)swap_log})
             if (p) (void)hipFree(p);
         for (size_t j = 0; j < part.size(); j++) {
             if (part[j].work) (void)hipFree(part[j].work);
@@ -946,6 +1014,7 @@ int main(int argc, char** argv) {
         I.greedy = ctl.greedy;
         I.kempe = ctl.kempe;
         I.kempe_max_chain = ctl.kempe_max_chain;
+        I.slot_swap = ctl.slot_swap;
     }
     std::vector<ncclComm_t> comms(K, nullptr);
     if (rccl) {
@@ -1072,6 +1141,11 @@ int main(int argc, char** argv) {
         for (int k = 0; k < K; k++) {
             check_hip(hipSetDevice(isl[k].device), "hipSetDevice");
             out.line(isl[k].unique_report(k, k));
+        }
+    if (ctl.slot_swap > 0)
+        for (int k = 0; k < K; k++) {
+            check_hip(hipSetDevice(isl[k].device), "hipSetDevice");
+            out.line(isl[k].slot_swap_report());
         }
     if (ctl.report)
         for (int k = 0; k < K; k++) {

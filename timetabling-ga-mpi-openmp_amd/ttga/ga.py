@@ -16,6 +16,9 @@ kernels (include/ttga.h):
   replacing a member (tt_ga_replace_unique): an addition, ga.cpp has no
   such test. Migration is unchanged: a migrant may duplicate a member of its
   destination;
+* optionally (Island(slot_swap=N)) every searched row goes through the
+  timeslot-swap descent (tt_slot_swap) before it is sorted in: an addition
+  too, which changes scv only;
 * migration (ga.cpp:514-540) and the final MIN reduction (ga.cpp:234-257) are
   in ttga.islands.
 
@@ -207,13 +210,21 @@ class Island(Members):
     a chain (0: no cap), on the sub-batch's stream directly after tt_ga_breed
     and before the search, drawing from the children's own streams. kempe=0
     issues no call at all. kempe_stats() reports what the moves did.
+
+    slot_swap=n >= 1: tt_slot_swap(max_passes=n) (include/ttga_slotswap.h) runs
+    on the part's stream directly behind every tt_local_search_eval -- on the
+    children of a sub-batch before it joins the pending ones, on the members in
+    initialize() before the sort -- and lowers their scv and penalty tensors
+    in place, so the replacement sorts on the true penalties with no second
+    evaluation. It draws no random numbers. slot_swap=0 issues no call at all.
+    slot_swap_stats() reports what the descents did.
     """
 
     def __init__(self, dp, pop_size: int = 10, children: int = 1, max_steps: int = 200, seed: int = 1,
                  p_cross: float = 0.8, p_mut: float = 0.5, skip_init_draws: bool = True, device=None,
                  p1: float = 1.0, p2: float = 1.0, p3: float = 0.0, lpt: bool | None = None, stream=None,
                  schedule: str = "batch", parts: int = 2, unique: bool = False, init: str = "random",
-                 kempe: float = 0.0, kempe_max_chain: int = 0):
+                 kempe: float = 0.0, kempe_max_chain: int = 0, slot_swap: int = 0):
         """stream: a torch.cuda.Stream of the island's own, or None (torch's current
         stream). Islands multiplexed on one GPU (ttga.islands --islands K) each take
         one, so one island's launches fill the SIMD slots another's local-search tail
@@ -227,6 +238,8 @@ class Island(Members):
             raise ValueError("kempe must be a probability in [0, 1]")
         if int(kempe_max_chain) < 0:
             raise ValueError("kempe_max_chain must be >= 0 (0: no cap)")
+        if int(slot_swap) < 0:
+            raise ValueError("slot_swap must be >= 0 (0: off)")
         if not (1 <= children <= pop_size):
             raise ValueError("need 1 <= children <= pop_size")
         if schedule not in ("batch", "staggered"):
@@ -249,6 +262,7 @@ class Island(Members):
         self.unique = bool(unique)
         self.init = init
         self.kempe, self.kempe_max_chain = float(kempe), int(kempe_max_chain)
+        self.slot_swap = int(slot_swap)
         self.generation = 0
         self.schedule = schedule
         self.parts = int(parts) if schedule == "staggered" else 1
@@ -292,6 +306,20 @@ class Island(Members):
                 p.kempe_sums = torch.zeros(3, dtype=torch.int64, device=dev)
                 self._extra += [p.chain, p.kempe_sums]
         self._kempe_children = 0
+        # slot_swap: each part's (and the members') gains and passes and the running (rows
+        # improved, passes, gain), added up on the stream behind the call; the rows, on the host
+        if self.slot_swap > 0:
+            self._swap_init = types.SimpleNamespace(
+                gain=torch.zeros(self.N, dtype=torch.int32, device=dev),
+                passes=torch.zeros(self.N, dtype=torch.int32, device=dev),
+                sums=torch.zeros(3, dtype=torch.int64, device=dev))
+            self._extra += list(vars(self._swap_init).values())
+            for p in self._parts:
+                p.swap = types.SimpleNamespace(gain=torch.zeros(p.n, dtype=torch.int32, device=dev),
+                                               passes=torch.zeros(p.n, dtype=torch.int32, device=dev),
+                                               sums=torch.zeros(3, dtype=torch.int64, device=dev))
+                self._extra += list(vars(p.swap).values())
+        self._swap_rows = 0
         self._replaced = 0
         self._pending = []                            # parts searched but not yet replaced, in breed order
         self._last_replace = 0                        # part whose work buffer holds the last replace's source
@@ -409,6 +437,8 @@ class Island(Members):
                 self.dp.random_init(self.rng_init, p["slot"], p["room"])
             self.dp.local_search(p["slot"], p["room"], self.rng_init, self.max_steps, self.p1, self.p2, self.p3,
                                  out=(p["hcv"], p["scv"], p["feasible"], p["penalty"]))
+            if self.slot_swap > 0:
+                self._slot_swap(p, self._swap_init)
             if self.unique:
                 self.dp.ga_replace_unique(p, None, self.work, n_kept=self._init_kept)
             else:
@@ -453,6 +483,8 @@ class Island(Members):
             if self.kempe > 0:
                 self._kempe(p)
             self._search(p.child, p.rng, p.work)
+            if self.slot_swap > 0:
+                self._slot_swap(p.child, p.swap)
             self._pending.append(j)
             if len(self._pending) >= self.parts:
                 self._replace_oldest()
@@ -464,6 +496,28 @@ class Island(Members):
         self.dp.kempe_move(p.child["slot"], p.child["room"], p.rng, self.kempe, self.kempe_max_chain, p.chain)
         p.kempe_sums += torch.stack([(p.chain > 0).sum(), (p.chain < 0).sum(), p.chain.clamp(min=0).sum()])
         self._kempe_children += p.n
+
+    def _slot_swap(self, rows, b):
+        """tt_slot_swap on the searched rows (on the current stream, behind
+        their search and evaluation) and its counts, summed on the device
+        behind the call."""
+        import torch
+        self.dp.slot_swap(rows["slot"], self.slot_swap, scv=rows["scv"], penalty=rows["penalty"], gain=b.gain,
+                          passes=b.passes)
+        b.sums += torch.stack([(b.passes > 0).sum(), b.passes.sum(), b.gain.sum()])
+        self._swap_rows += int(rows["slot"].shape[0])
+
+    def slot_swap_stats(self) -> dict:
+        """Island(slot_swap > 0): the rows tt_slot_swap was called on, how many
+        of them it improved, the swaps applied and the scv gained in all, as
+        Python ints. Pending sub-batches are replaced first; synchronises."""
+        if not self.slot_swap > 0:
+            raise ValueError("slot_swap_stats() needs Island(slot_swap > 0)")
+        self.flush()
+        self.sync()
+        improved, passes, gain = (int(v) for v in sum(b.sums.cpu() for b in [self._swap_init]
+                                                      + [p.swap for p in self._parts]).tolist())
+        return {"rows": int(self._swap_rows), "improved": improved, "passes": passes, "gain": gain}
 
     def kempe_stats(self) -> dict:
         """Island(kempe > 0): the children tt_kempe_move was called on, how many
@@ -667,6 +721,15 @@ def kempe_line(stats: dict) -> str:
     return json_line({"kempe": {"children": int(stats["children"]), "moved": moved,
                                 "rejected": int(stats["rejected"]),
                                 "meanChain": float(stats["chain_events"]) / moved if moved else 0.0}})
+
+
+def slot_swap_line(stats: dict) -> str:
+    """The drivers' --slot-swap line of one island: Island.slot_swap_stats()
+    with the mean number of swaps over the improved rows (0 when there are none)."""
+    improved = int(stats["improved"])
+    return json_line({"slotSwap": {"gain": int(stats["gain"]), "improved": improved,
+                                   "meanPasses": float(stats["passes"]) / improved if improved else 0.0,
+                                   "rows": int(stats["rows"])}})
 
 
 def run_final_line(procs: int, threads: int, total_time: float) -> str:

@@ -28,6 +28,10 @@ Reference correspondence:
   search, chains of more than N events refused, 0 = no cap; each island then
   prints a `kempe` line after its solution line: children, chains moved,
   chains refused, mean length of the chains moved),
+  `--slot-swap N` (tt_slot_swap, include/ttga_slotswap.h, with max_passes N
+  directly behind every local search, ttga.ga.Island(slot_swap=N); each island
+  then prints a `slotSwap` line after the solution, kempe and unique lines:
+  rows, rows improved, mean swaps per improved row, scv gained; 0: no call),
   `--stagger` / `--stagger-parts P` (the children of a generation as 2 / P
   sub-batches on as many streams, each bred P - 1 sub-batches behind:
   ttga.ga.Island's staggered schedule),
@@ -100,6 +104,17 @@ def parse_control(argv, out=sys.stdout, err=sys.stderr) -> dict:
                 raise SystemExit(1)
             extra[k[2:].replace("-", "_")] = v
             del args[i:i + 2]
+    if "--slot-swap" in args:             # include/ttga_slotswap.h
+        i = args.index("--slot-swap")
+        try:
+            v = int(args[i + 1])
+        except (IndexError, ValueError):
+            v = -1
+        if not 0 <= v <= 2 ** 31 - 1:
+            err.write("Error: --slot-swap must be a non-negative integer\n")
+            raise SystemExit(1)
+        extra["slot_swap"] = v
+        del args[i:i + 2]
     if len(args) % 2 != 0:
         err.write("Parse error: Number of command line parameters incorrect\nUsage:\n" + USAGE + "\n")
         raise SystemExit(1)
@@ -241,8 +256,8 @@ def main(argv=None):
     import torch.distributed as dist
 
     from . import instance as tim
-    from .ga import (CostLog, Island, kempe_line, max_steps_for, run_best_line, run_final_line, solution_line,
-                     unique_line)
+    from .ga import (CostLog, Island, kempe_line, max_steps_for, run_best_line, run_final_line, slot_swap_line,
+                     solution_line, unique_line)
 
     from .native import DeviceProblem
 
@@ -295,7 +310,8 @@ def main(argv=None):
                       seed=rank_seed(seed, rank * K + k), p1=ctl["p1"], p2=ctl["p2"], p3=ctl["p3"],
                       stream=streams[k], schedule="staggered" if parts >= 2 else "batch", parts=max(parts, 2),
                       unique=bool(ctl.get("unique")), init=ctl.get("init", "random"),
-                      kempe=ctl.get("kempe", 0.0), kempe_max_chain=ctl.get("kempe_max_chain", 0))
+                      kempe=ctl.get("kempe", 0.0), kempe_max_chain=ctl.get("kempe_max_chain", 0),
+                      slot_swap=ctl.get("slot_swap", 0))
                for k in range(K)]
     if rank == 0:
         islands[0].initialize()
@@ -346,6 +362,9 @@ def main(argv=None):
     if ctl.get("unique"):
         for k, isl in enumerate(islands):
             out.write(unique_line(isl.unique_stats(), rank * K + k, k) + "\n")
+    if ctl.get("slot_swap", 0) > 0:
+        for isl in islands:
+            out.write(slot_swap_line(isl.slot_swap_stats()) + "\n")
     if ctl.get("report"):
         from .report import report_line
         for k, isl in enumerate(islands):

@@ -40,6 +40,9 @@ GREEDY_EXPORTS = ("tt_greedy_work_bytes", "tt_greedy_order", "tt_greedy_init")
 # include/ttga_kempe.h
 KEMPE_EXPORTS = ("tt_kempe_move",)
 
+# include/ttga_slotswap.h
+SLOTSWAP_EXPORTS = ("tt_slot_swap",)
+
 _lib = None
 
 
@@ -107,6 +110,8 @@ def load(path: os.PathLike | str | None = None) -> ctypes.CDLL:
     lib.tt_greedy_init.restype = ctypes.c_int
     lib.tt_kempe_move.argtypes = [vp, vp, vp, vp, i32, dbl, i32, vp, vp]
     lib.tt_kempe_move.restype = ctypes.c_int
+    lib.tt_slot_swap.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.tt_slot_swap.restype = ctypes.c_int
     for name in EXPORTS:
         if name not in ("tt_last_error", "tt_ga_work_bytes", "tt_ga_work_source_offset"):
             getattr(lib, name).restype = ctypes.c_int
@@ -451,6 +456,26 @@ class DeviceProblem:
         _check(self.lib, self.lib.tt_kempe_move(
             self.handle, slot.data_ptr(), room.data_ptr(), rng.data_ptr(), P, float(prob), int(max_chain),
             ctypes.c_void_p(chain_len.data_ptr() if chain_len is not None else None), self._stream(slot)))
+
+    # -- timeslot-swap descent (include/ttga_slotswap.h) ------------------------------
+    def slot_swap(self, slot, max_passes, scv=None, penalty=None, gain=None, passes=None, perm=None):
+        """tt_slot_swap in place on slot [P, E]: per row, the pair of timeslots
+        whose exchange lowers scv most trades its events, at most max_passes
+        times. scv, penalty (int32 [P], updated in place), gain, passes (int32
+        [P]) and perm (uint8 [P, 45], new slot = perm[old slot]) are optional
+        CUDA tensors."""
+        import torch
+        P = self._pop(slot)
+        for name, t in (("scv", scv), ("penalty", penalty), ("gain", gain), ("passes", passes)):
+            if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == P
+                                      and t.device == slot.device):
+                raise ValueError(f"{name} must be a contiguous int32 CUDA tensor of P entries on the population's device")
+        if perm is not None and not (perm.is_cuda and perm.dtype == torch.uint8 and perm.is_contiguous()
+                                     and tuple(perm.shape) == (P, NUM_SLOTS) and perm.device == slot.device):
+            raise ValueError("perm must be a contiguous uint8 CUDA tensor of shape [P, 45] on the population's device")
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)    # noqa: E731
+        _check(self.lib, self.lib.tt_slot_swap(self.handle, slot.data_ptr(), P, int(max_passes), ptr(scv), ptr(penalty),
+                                               ptr(gain), ptr(passes), ptr(perm), self._stream(slot)))
 
     @staticmethod
     def _rng(rng, P):

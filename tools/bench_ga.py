@@ -26,6 +26,7 @@ slots, rooms, hcv, scv, feasible, penalty and final RNG states
                              [--gens 3] [--steps 200] [--cpu-sample 512]
                              [--warm-gens N] [--warm-feasible F] [--unique]
                              [--init random|greedy] [--kempe P] [--kempe-max-chain N]
+                             [--slot-swap N]
 
 --warm-gens / --warm-feasible run untimed generations first, until a fraction F
 of the population is feasible (or N generations), so the timed generations
@@ -42,6 +43,10 @@ record then carries "init" and the feasible share right after initialize().
 "kempe" (the probability, the cap, the children, the chains moved and rejected
 and their mean length). Its populations part from the plain run's at the first
 chain moved, so the two runs' times are not like for like.
+--slot-swap N runs Island(slot_swap=N): tt_slot_swap (include/ttga_slotswap.h)
+with max_passes N behind every search; the record then carries "slot_swap" (N,
+the rows, the rows improved, the mean swaps per improved row and the scv
+gained). Its populations part from the plain run's at the first swap applied.
 """
 import argparse
 import json
@@ -98,6 +103,8 @@ def parser():
     ap.add_argument("--kempe", type=float, default=0.0,
                     help="probability of tt_kempe_move per child (Island(kempe=...)); 0: never called")
     ap.add_argument("--kempe-max-chain", type=int, default=0, help="the cap on a chain's length (0: none)")
+    ap.add_argument("--slot-swap", type=int, default=0,
+                    help="max_passes of tt_slot_swap behind every search (Island(slot_swap=...)); 0: never called")
     return ap
 
 
@@ -111,7 +118,7 @@ def run_ga(a):
     isls = [Island(dp, pop_size=a.pop, children=a.children, max_steps=a.steps, seed=seeds[k],
                    lpt=None if a.lpt == "auto" else a.lpt == "on", stream=torch.cuda.Stream() if K > 1 else None,
                    schedule=a.schedule, parts=a.parts, unique=a.unique, init=a.init, kempe=a.kempe,
-                   kempe_max_chain=a.kempe_max_chain)
+                   kempe_max_chain=a.kempe_max_chain, slot_swap=a.slot_swap)
             for k in range(K)]
     isl = isls[0]
     torch.cuda.synchronize()
@@ -187,8 +194,13 @@ def run_ga(a):
         out["kempe"] = {"prob": a.kempe, "max_chain": a.kempe_max_chain, "children": k["children"],
                         "moved": k["moved"], "rejected": k["rejected"],
                         "mean_chain": k["chain_events"] / k["moved"] if k["moved"] else 0.0}
+    if a.slot_swap > 0:
+        stats = [i.slot_swap_stats() for i in isls]
+        k = {key: sum(s[key] for s in stats) for key in ("rows", "improved", "passes", "gain")}
+        out["slot_swap"] = {"max_passes": a.slot_swap, "rows": k["rows"], "improved": k["improved"], "gain": k["gain"],
+                            "mean_passes": k["passes"] / k["improved"] if k["improved"] else 0.0}
     R = ref()
-    if R is not None and a.cpu_sample > 0 and not a.kempe > 0:
+    if R is not None and a.cpu_sample > 0 and not a.kempe > 0 and not a.slot_swap > 0:
         n = min(a.cpu_sample, a.children)
         threads, total, model = host_cores()
         h = R.problem(inst)

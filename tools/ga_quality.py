@@ -36,6 +36,13 @@ the plain island, same seeds and parameters, no reference run: final values
 (Mann-Whitney U, two-sided), their medians, the medians of the logged best at
 generation checkpoints, and per run the chains moved, rejected and their mean
 length.
+
+--slot-swap N does the same for the timeslot-swap descent: Island(slot_swap=N)
+(tt_slot_swap, include/ttga_slotswap.h, max_passes N behind every search)
+against the plain island, same seeds and parameters, no reference run: final
+values (Mann-Whitney U, two-sided), their medians, the medians of the logged
+best at generation checkpoints, and per run the rows, the rows improved, the
+swaps applied and the scv gained.
 """
 import argparse
 import json
@@ -65,7 +72,7 @@ def summarize(final, feas, trace, checkpoints):
 
 
 def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch", unique=False, stats_out=None,
-                init="random", kempe=0.0, kempe_max_chain=0):
+                init="random", kempe=0.0, kempe_max_chain=0, slot_swap=0):
     import torch
 
     from ttga import native
@@ -77,7 +84,8 @@ def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch", uni
     secs = []
     for k, s in enumerate(seeds):
         isl = Island(dp, pop_size=pop, children=children, max_steps=steps, seed=int(s), schedule=schedule,
-                     unique=unique, init=init, kempe=kempe, kempe_max_chain=kempe_max_chain)
+                     unique=unique, init=init, kempe=kempe, kempe_max_chain=kempe_max_chain,
+                     slot_swap=slot_swap)
         tr = torch.zeros(gens + 1, dtype=torch.int64, device="cuda")
         p = isl.pop
 
@@ -100,7 +108,9 @@ def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch", uni
         feas[k] = 1 if isl.member_meta(0)[0] else 0
         final[k] = trace[k, -1]
         if stats_out is not None:
-            if kempe > 0:
+            if slot_swap > 0:
+                stats_out.append(isl.slot_swap_stats())
+            elif kempe > 0:
                 stats_out.append(isl.kempe_stats())
             elif unique:
                 stats_out.append(isl.unique_stats())
@@ -131,6 +141,8 @@ def main():
     ap.add_argument("--kempe", type=float, default=0.0,
                     help="P > 0: compare Island(kempe=P) with the plain island (no reference run)")
     ap.add_argument("--kempe-max-chain", type=int, default=0, help="the cap on a chain's length (0: none)")
+    ap.add_argument("--slot-swap", type=int, default=0,
+                    help="N > 0: compare Island(slot_swap=N) with the plain island (no reference run)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     from scipy import stats
@@ -213,6 +225,31 @@ def main():
         res["tests"] = {"kempe_vs_plain": {
             "final_value_mannwhitney_p": 1.0 if same else float(stats.mannwhitneyu(vk, vp, alternative="two-sided").pvalue),
             "median_kempe": float(np.median(vk)), "median_plain": float(np.median(vp))}}
+        print(json.dumps(res), flush=True)
+        if a.out:
+            pathlib.Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
+        return
+    if a.slot_swap > 0:
+        dg = a.device_gens or a.gens
+        res["children_per_generation"], res["generations"] = a.device_children, dg
+        res["slot_swap"] = a.slot_swap
+        cps = sorted({0, 1, 10, 100, dg // 2, dg} & set(range(dg + 1)))
+        for name, n in (("device", 0), ("device_slot_swap", a.slot_swap)):
+            st = [] if n > 0 else None
+            final, feas, trace, secs = device_runs(inst, seeds, a.pop, dg, a.steps, a.device_children,
+                                                   a.device_schedule, stats_out=st, slot_swap=n)
+            res["runs"][name] = summarize(final, feas, trace, cps)
+            res["runs"][name]["seconds_per_run"] = secs
+            if st:
+                res["runs"][name]["slot_swap_stats"] = st
+                improved, passes = sum(s["improved"] for s in st), sum(s["passes"] for s in st)
+                res["runs"][name]["mean_passes"] = passes / improved if improved else 0.0
+                res["runs"][name]["improved_share"] = improved / max(1, sum(s["rows"] for s in st))
+        vp, vs = (np.array(res["runs"][n]["final_log_value"]) for n in ("device", "device_slot_swap"))
+        same = bool(np.array_equal(vp, vs))
+        res["tests"] = {"slot_swap_vs_plain": {
+            "final_value_mannwhitney_p": 1.0 if same else float(stats.mannwhitneyu(vs, vp, alternative="two-sided").pvalue),
+            "median_slot_swap": float(np.median(vs)), "median_plain": float(np.median(vp))}}
         print(json.dumps(res), flush=True)
         if a.out:
             pathlib.Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
