@@ -34,6 +34,7 @@ namespace ttga {
 
 typedef __attribute__((address_space(4))) const uint32_t ConstU32;
 typedef __attribute__((address_space(4))) const int32_t ConstI32;
+typedef __attribute__((address_space(3))) unsigned long long LdsU64;
 
 // ---------------------------------------------------------------- eval_tile5
 // Slot-row DMA and room rows by buffer instructions (per-tile resource, 32-bit
@@ -56,7 +57,14 @@ typedef __attribute__((address_space(4))) const int32_t ConstI32;
 //    (ds_or_b64), room-cell counters (packed u16, ds_add_rtn), unsuitable
 //    rooms, last-slot term, and the correlated same-slot pairs as
 //    popcount(cupT[w][i] & B[slot_i][w]) over the upper-triangle words, which
-//    (with possibleRooms and studentNumber) stay in registers for the launch;
+//    (with possibleRooms and studentNumber) stay in registers for the launch.
+//    Per individual the wave clears its workspace with ds_write_addtid_b32
+//    pieces (t5_clear_pieces below: no address register, a quarter of the
+//    store-data transfer of 16-byte stores) and forms ONE LDS address per event
+//    word, row[r] = B + slot_r * 8 EWC: the bitset OR of word r and every
+//    correlation read of that event's row carry the word index as the
+//    instruction's immediate offset, so the slot values are dead after the
+//    per-event block;
 //  * an individual with an invalid gene is detected from registers before any
 //    LDS work (its outputs are the -1 sentinels); the valid path has no
 //    per-event branches except on the last, partial event word;
@@ -81,45 +89,15 @@ __device__ __forceinline__ int popc_acc(uint64_t x, int acc) {
 __device__ __forceinline__ uint32_t lds_addr(const void* p) {
     return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
 }
-// N consecutive 64-bit LDS words at byte address addr, as N single
-// ds_read_b64 (the compiler would pair them into ds_read2_b64) with the wait
-// in the same asm block, so the results are defined when it ends.
-#define TT_RD(k, o) "ds_read_b64 %" #k ", %" #o " offset:" #k "*8\n"
-template <int N>
-__device__ __forceinline__ void lds_row_b64(uint32_t addr, uint64_t* v) {
-    static_assert(N >= 1 && N <= 7, "1..7 words");
-    uint64_t d[7];
-    if constexpr (N == 7)
-        asm volatile(TT_RD(0, 7) TT_RD(1, 7) TT_RD(2, 7) TT_RD(3, 7) TT_RD(4, 7) TT_RD(5, 7) TT_RD(6, 7) "s_waitcnt lgkmcnt(0)"
-                     : "=&v"(d[0]), "=&v"(d[1]), "=&v"(d[2]), "=&v"(d[3]), "=&v"(d[4]), "=&v"(d[5]), "=&v"(d[6])
-                     : "v"(addr) : "memory");
-    else if constexpr (N == 6)
-        asm volatile(TT_RD(0, 6) TT_RD(1, 6) TT_RD(2, 6) TT_RD(3, 6) TT_RD(4, 6) TT_RD(5, 6) "s_waitcnt lgkmcnt(0)"
-                     : "=&v"(d[0]), "=&v"(d[1]), "=&v"(d[2]), "=&v"(d[3]), "=&v"(d[4]), "=&v"(d[5]) : "v"(addr) : "memory");
-    else if constexpr (N == 5)
-        asm volatile(TT_RD(0, 5) TT_RD(1, 5) TT_RD(2, 5) TT_RD(3, 5) TT_RD(4, 5) "s_waitcnt lgkmcnt(0)"
-                     : "=&v"(d[0]), "=&v"(d[1]), "=&v"(d[2]), "=&v"(d[3]), "=&v"(d[4]) : "v"(addr) : "memory");
-    else if constexpr (N == 4)
-        asm volatile(TT_RD(0, 4) TT_RD(1, 4) TT_RD(2, 4) TT_RD(3, 4) "s_waitcnt lgkmcnt(0)"
-                     : "=&v"(d[0]), "=&v"(d[1]), "=&v"(d[2]), "=&v"(d[3]) : "v"(addr) : "memory");
-    else if constexpr (N == 3)
-        asm volatile(TT_RD(0, 3) TT_RD(1, 3) TT_RD(2, 3) "s_waitcnt lgkmcnt(0)"
-                     : "=&v"(d[0]), "=&v"(d[1]), "=&v"(d[2]) : "v"(addr) : "memory");
-    else if constexpr (N == 2)
-        asm volatile(TT_RD(0, 2) TT_RD(1, 2) "s_waitcnt lgkmcnt(0)" : "=&v"(d[0]), "=&v"(d[1]) : "v"(addr) : "memory");
-    else
-        asm volatile(TT_RD(0, 1) "s_waitcnt lgkmcnt(0)" : "=&v"(d[0]) : "v"(addr) : "memory");
-#pragma unroll
-    for (int k = 0; k < N; ++k) v[k] = d[k];
-}
-#undef TT_RD
-
-// NA consecutive 64-bit LDS words at byte address a and NB at b (NA + NB <= 8),
-// all in flight at once, waited for inside the asm.
+// 64-bit LDS words in single ds_read_b64 (the compiler would pair them into
+// ds_read2_b64), all in flight at once, with the wait in the same asm block, so
+// the results are defined when it ends: NA consecutive words from byte address
+// a + OA and NB from b + OB (NA + NB <= 8). OA and OB go into the instructions'
+// immediate offsets, so a and b can be row addresses that serve every word.
 #define TT_O(k) [d##k] "=&v"(d[k])
-#define TT_I(k) [x##k] "v"(k < NA ? a : b), [o##k] "i"(k < NA ? 8 * k : 8 * (k - NA))
+#define TT_I(k) [x##k] "v"(k < NA ? a : b), [o##k] "i"(k < NA ? OA + 8 * k : OB + 8 * (k - NA))
 #define TT_R(k) "ds_read_b64 %[d" #k "], %[x" #k "] offset:%[o" #k "]\n"
-template <int NA, int NB>
+template <int NA, int NB, int OA, int OB>
 __device__ __forceinline__ void lds_two_rows(uint32_t a, uint32_t b, uint64_t* v) {
     constexpr int N = NA + NB;
     static_assert(NA >= 1 && NB >= 0 && N <= 8, "1..8 words");
@@ -157,32 +135,28 @@ __device__ __forceinline__ void lds_two_rows(uint32_t a, uint32_t b, uint64_t* v
 #undef TT_R
 
 // Correlated same-slot pairs of the lane's events:
-// h += popcount(cupT upper words & B[slot] words). Event words R and EWC-1-R
-// are read together (EWC+1 row words in one asm block): ceil(EWC/2) LDS round
-// trips per individual instead of EWC.
+// h += popcount(cupT upper words & B[slot] words). row[r] is the LDS byte
+// address of B row slot_r of the lane's event in word r (the row of slot 0,
+// against zero cup words, for the lanes of a partial last word beyond E); word w
+// of a row is the immediate offset 8 * w. Event words R and EWC-1-R are read
+// together (EWC+1 row words in one asm block): ceil(EWC/2) LDS round trips per
+// individual instead of EWC.
 template <int R, int EWC>
-__device__ __forceinline__ void corr_words(uint32_t bbase, const uint32_t* sv, const uint64_t (*cup)[EWC], int lane,
-                                           int E, bool last_partial, int& h) {
+__device__ __forceinline__ void corr_words(const uint32_t* row, const uint64_t (*cup)[EWC], int& h) {
     constexpr int S = EWC - 1 - R;                     // partner word
     if constexpr (R < S) {
-        // word S may be the last, partial one: its lanes beyond E read row 0 (harmless,
-        // their cup words are zero)
-        const uint32_t ss = (S < EWC - 1 || !last_partial || lane + 64 * S < E) ? sv[S] : 0u;
         uint64_t bw[EWC + 1];
-        lds_two_rows<EWC - R, EWC - S>(bbase + sv[R] * (uint32_t)(EWC * 8) + 8 * R,
-                                       bbase + ss * (uint32_t)(EWC * 8) + 8 * S, bw);
+        lds_two_rows<EWC - R, EWC - S, 8 * R, 8 * S>(row[R], row[S], bw);
 #pragma unroll
         for (int w = R; w < EWC; ++w) h = popc_acc(cup[R][w] & bw[w - R], h);
 #pragma unroll
         for (int w = S; w < EWC; ++w) h = popc_acc(cup[S][w] & bw[EWC - R + w - S], h);
-        corr_words<R + 1, EWC>(bbase, sv, cup, lane, E, last_partial, h);
+        corr_words<R + 1, EWC>(row, cup, h);
     } else if constexpr (R == S) {
-        if (R < EWC - 1 || !last_partial || lane + 64 * R < E) {
-            uint64_t bw[EWC - R];
-            lds_row_b64<EWC - R>(bbase + sv[R] * (uint32_t)(EWC * 8) + 8 * R, bw);
+        uint64_t bw[EWC - R];
+        lds_two_rows<EWC - R, 0, 8 * R, 0>(row[R], row[R], bw);
 #pragma unroll
-            for (int w = R; w < EWC; ++w) h = popc_acc(cup[R][w] & bw[w - R], h);
-        }
+        for (int w = R; w < EWC; ++w) h = popc_acc(cup[R][w] & bw[w - R], h);
     }
 }
 
@@ -432,6 +406,53 @@ __device__ __forceinline__ uint32_t mad_u16_hi(uint32_t a, uint32_t b, uint32_t 
     return d;
 }
 
+// Clearing a wave's workspace (WS bytes at LDS address a): ds_write_addtid_b32
+// stores a dword per lane at M0[15:0] + immediate offset + 4 * lane with no
+// address register, 256 B for 2 LDS-pipe cycles (a ds_write_b128 moves five
+// source dwords for its 1 KiB: about 13). floor(WS / 256) such pieces, unrolled
+// with their offsets as immediates and entered by one computed jump (WS depends
+// on R; at most t5_clear_max pieces), then one full-wave ds_write_b32 over the
+// last 256 B, which overlaps the pieces where WS is no multiple of 256: nothing
+// outside [a, a + WS) is written. M0 holds 16 bits and a workspace can lie above
+// 64 KiB, so there are two copies of the pieces: offsets from a, and offsets
+// + kT5ClrBias from a - kT5ClrBias for a >= 64 KiB (every workspace lies below
+// kT5ClrReach; tt_eval_variant checks it). M0, which the LDS-DMA uses too, is
+// saved and restored inside the one asm statement.
+constexpr uint32_t kT5ClrBias = 0x8000u;
+constexpr size_t kT5ClrReach = 0x10000u + kT5ClrBias;   // the workspaces lie below this LDS address
+constexpr int t5_clear_max(int EWC, int PK) {          // most 256-B pieces: WS at the largest R of the PK form
+    return (kSlots * EWC * 8 + kSlots * (PK == 1 ? 8 : PK == 2 ? 16 : 32) * 4 + 15) / 256;
+}
+// m0v: a, or a - kT5ClrBias; skip: byte offset of the entry point behind the
+// s_getpc_b64 (12 B to the first copy's first store, 8 B per store, 4 for the branch)
+template <int MAXF>
+__device__ __forceinline__ void t5_clear_pieces(uint32_t m0v, uint32_t skip) {
+    uint32_t keep;
+    asm volatile("s_mov_b32 %[keep], m0\n"
+                 "s_mov_b32 m0, %[base]\n"
+                 "s_getpc_b64 vcc\n"
+                 "s_add_u32 vcc_lo, vcc_lo, %[skip]\n"
+                 "s_addc_u32 vcc_hi, vcc_hi, 0\n"
+                 "s_setpc_b64 vcc\n"
+                 ".set tt_clr_k, %c[n]\n"
+                 ".rept %c[n]\n"
+                 ".set tt_clr_k, tt_clr_k-1\n"
+                 "ds_write_addtid_b32 %[z] offset:tt_clr_k*256\n"
+                 ".endr\n"
+                 "s_branch .Ltt_clr_end%=\n"
+                 ".set tt_clr_k, %c[n]\n"
+                 ".rept %c[n]\n"
+                 ".set tt_clr_k, tt_clr_k-1\n"
+                 "ds_write_addtid_b32 %[z] offset:tt_clr_k*256+%c[bias]\n"
+                 ".endr\n"
+                 ".Ltt_clr_end%=:\n"
+                 "s_mov_b32 m0, %[keep]\n"
+                 "s_nop 0"
+                 : [keep] "=&s"(keep)
+                 : [base] "s"(m0v), [skip] "s"(skip), [z] "v"(0u), [n] "i"(MAXF), [bias] "i"(kT5ClrBias)
+                 : "memory", "scc", "vcc");
+}
+
 // Issue priority falls as a wave gets through its tile (3 in the
 // lane phase, then 3, 3, 2, 2, 1, 1, 0, 0 over its wave-phase individuals), so
 // of a CU's two resident workgroups the one further behind wins the arbiter --
@@ -478,6 +499,12 @@ __global__ __launch_bounds__(64 * NW, 4) void eval_tile5_kernel(DevProblem pb, c
     const int tiles = (P + 63) / 64;
     const bool last_partial = E < 64 * EWC;                   // lanes of word EWC-1 beyond E
     const int RW = (R + 1) / 2;
+    // workspace clear (t5_clear_pieces): M0 value and entry point, the same for every individual
+    constexpr int CLRF = t5_clear_max(EWC, PK);
+    const uint32_t ws_a = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_addr(ws));
+    const bool ws_hi = ws_a >= 0x10000u;
+    const uint32_t clr_m0 = ws_hi ? ws_a - kT5ClrBias : ws_a;
+    const uint32_t clr_skip = 12u + 8u * (uint32_t)(CLRF - min(L.WS >> 8, CLRF)) + (ws_hi ? 8u * CLRF + 4u : 0u);
 
     using PossT = typename std::conditional<PK == 0, uint64_t, uint32_t>::type;
     uint64_t inv_cup[EWC][EWC];
@@ -595,8 +622,16 @@ __global__ __launch_bounds__(64 * NW, 4) void eval_tile5_kernel(DevProblem pb, c
             const bool any_bad = wave_any(smax >= (uint32_t)kSlots || rmax >= (uint32_t)R);
             int h = 0, last = 0;
             if (!any_bad) {
-                if (!(ablate & 32))
-                    for (int c = lane; c < (L.WS >> 4); c += 64) ((uint4*)ws)[c] = make_uint4(0u, 0u, 0u, 0u);
+                // B row of each event's slot (row 0 for the lanes of a partial last word beyond
+                // E, whose slot reads as 0): one address per event word serves the bitset OR and
+                // every correlation read, the word index going into the immediate offset
+                uint32_t row[EWC];
+#pragma unroll
+                for (int r = 0; r < EWC; ++r) row[r] = lds_addr(B) + __umul24(sv[r], (uint32_t)(EWC * 8));
+                if (!(ablate & 32)) {
+                    t5_clear_pieces<CLRF>(clr_m0, clr_skip);
+                    *(uint32_t*)(ws + L.WS - 256 + 4 * lane) = 0u;
+                }
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -604,7 +639,9 @@ __global__ __launch_bounds__(64 * NW, 4) void eval_tile5_kernel(DevProblem pb, c
                 for (int r = 0; r < EWC; ++r) {
                     if (r < EWC - 1 || !last_partial || lane + 64 * r < E) {
                         const uint32_t s = sv[r], ro = rv[r];
-                        if (!(ablate & 8)) atomicOr((unsigned long long*)&B[s * EWC + r], 1ull << lane);
+                        if (!(ablate & 8))
+                            __hip_atomic_fetch_or((LdsU64*)(uintptr_t)row[r] + r, 1ull << lane, __ATOMIC_RELAXED,
+                                                  __HIP_MEMORY_SCOPE_AGENT);
                         if (!(ablate & 16)) {                                   // Solution.cpp:148-150
                             // dword s*RW + ro/2: byte offset 2*(s*2RW + (ro & ~1))
                             uint32_t* c = (uint32_t*)((uint8_t*)cnt + ((__umul24(s, (uint32_t)(2 * RW)) + (ro & ~1u)) << 1));
@@ -628,7 +665,7 @@ __global__ __launch_bounds__(64 * NW, 4) void eval_tile5_kernel(DevProblem pb, c
                 if (!(ablate & 4)) {
                     // B-row words by single ds_read_b64 (2 LDS cycles per 512 B, 64 banks),
                     // not the ds_read2_b64 pairs the compiler forms (8 cycles per 1 KiB, 32 banks)
-                    corr_words<0, EWC>(lds_addr(B), sv, inv_cup, lane, E, last_partial, h);   // :151-153
+                    corr_words<0, EWC>(row, inv_cup, h);   // :151-153
                 }
                 // one reduction of h << 16 | last when every lane's two parts are < 1024
                 // (so both 64-lane sums stay below 2^16), else two
@@ -1095,7 +1132,8 @@ static size_t block_lds_bytes(int E, int R) {
 using namespace ttga;
 
 static bool tile5_fits(const tt_problem* p, int NW) {
-    return p->dev.EW64 <= 7 && p->E <= 32767 && tile5_layout(p->E, p->R, NW).bytes <= (NW == 8 ? 80 : 160) * 1024;
+    return p->dev.EW64 <= 7 && p->E <= 32767 && tile5_layout(p->E, p->R, NW).bytes <= (NW == 8 ? 80 : 160) * 1024 &&
+           tile5_layout(p->E, p->R, NW, true).off_part <= kT5ClrReach;
 }
 
 static bool wide_fits(const tt_problem* p) {
@@ -1199,8 +1237,10 @@ extern "C" int tt_eval_variant(const tt_problem* p, const uint8_t* slot, const u
         // kernel keeps 2 workgroups per CU either way; the 4-wave kernel fits 4
         // per CU with one buffer, 2 with two.)
         const Tile5Layout L0 = tile5_layout(E, R, NW, false), L1 = tile5_layout(E, R, NW, true);
-        const bool db_ok = (E & 3) == 0 && (((uintptr_t)slot) & 3) == 0 && L1.bytes <= 160 * 1024;
-        if (p->dev.EW64 > 7 || L0.bytes > 160 * 1024 || E > 32767) {
+        // (off_part: the workspaces end within t5_clear_pieces' reach; they do at every E and R the byte limits admit)
+        const bool db_ok = (E & 3) == 0 && (((uintptr_t)slot) & 3) == 0 && L1.bytes <= 160 * 1024 &&
+                           L1.off_part <= kT5ClrReach;
+        if (p->dev.EW64 > 7 || L0.bytes > 160 * 1024 || L0.off_part > kT5ClrReach || E > 32767) {
             set_error("instance too large for the tile5 kernel");
             return TT_ERR_LIMIT;
         }

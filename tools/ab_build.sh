@@ -8,9 +8,9 @@ REV=$1; NAME=$2
 SRC=$(mktemp -d /tmp/ab_XXXX)
 mkdir -p "$SRC/x/csrc" "$SRC/include" "$REPO/ab_libs"
 if [ "$REV" = wt ]; then
-  cp "$REPO"/timetabling-ga-mpi-openmp_amd/csrc/* "$SRC/x/csrc/"; cp "$REPO"/include/ttga.h "$SRC/include/"
+  cp "$REPO"/timetabling-ga-mpi-openmp_amd/csrc/* "$SRC/x/csrc/"; cp "$REPO"/include/*.h "$SRC/include/"
 else
-  git -C "$REPO" archive "$REV" timetabling-ga-mpi-openmp_amd/csrc include/ttga.h | tar -x -C "$SRC"
+  git -C "$REPO" archive "$REV" timetabling-ga-mpi-openmp_amd/csrc include | tar -x -C "$SRC"
   mv "$SRC"/timetabling-ga-mpi-openmp_amd/csrc/* "$SRC/x/csrc/"
 fi
 mkdir -p "$SRC/obj"
