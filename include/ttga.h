@@ -121,7 +121,19 @@ int tt_random_init(const tt_problem* p, int64_t* rng, uint8_t* slot, uint8_t* ro
 int tt_crossover(const tt_problem* p, const uint8_t* slot1, const uint8_t* slot2, int64_t* rng, uint8_t* slot,
                  uint8_t* room, int P, void* stream);
 
-/* Solution::mutation -> randomMove (Solution.cpp:441-469,912-914), in place. */
+/* Solution::mutation -> randomMove (Solution.cpp:441-469,912-914), in place:
+ * the move type (1..3) and the first event are drawn, then a timeslot (Move1)
+ * or one or two further events (Move2, Move3), each redrawn while it equals an
+ * earlier one; the touched timeslots get their rooms re-assigned.
+ * Below three events the reference never returns: Move2 at E = 1 and Move3 at
+ * E <= 2 redraw for ever. Here each rejection loop gives up after 2^20 redraws
+ * (the stream has then advanced by the first draw and those 2^20) and the move
+ * is applied with the coinciding events, in the order t = slot[e1];
+ * slot[e1] = slot[e2]; slot[e2] = slot[e3]; slot[e3] = t (Move2: without the
+ * e3 line, slot[e2] = t). So at E = 1 the row is unchanged, and at E = 2 Move3
+ * leaves the row unchanged where e3 == e1 (the last write undoes the first) and
+ * exchanges the two events' slots where e3 == e2. For E >= 3 a loop meets its
+ * bound with probability below 2^-600000: results equal the reference's. */
 int tt_mutation(const tt_problem* p, uint8_t* slot, uint8_t* room, int64_t* rng, int P, void* stream);
 
 /* Solution::localSearch(maxSteps, LS_limit, p1, p2, p3) (Solution.cpp:471-769)
@@ -179,7 +191,10 @@ int tt_lpt_order(const tt_problem* p, const int32_t* key, int n, int32_t* order,
  * crossover of the two parents : copy of the first (ga.cpp:562-566), then
  * next() < p_mut ? randomMove (ga.cpp:569-571). Children come out with rooms
  * assigned, ready for tt_local_search + tt_eval. child_flags u8[C] (scratch:
- * bit 0 crossed, bit 1 mutated). */
+ * bit 0 crossed, bit 1 mutated). The randomMove is tt_mutation's: below three
+ * events, where the reference's never returns, its rejection loops give up
+ * after 2^20 redraws and the move is applied with the coinciding events (see
+ * tt_mutation); a p_mut of 0 draws the mutation's next() and nothing more. */
 int tt_ga_breed(const tt_problem* p, const uint8_t* pop_slot, const uint8_t* pop_room, const int32_t* pop_penalty,
                 int N, int64_t* rng, int C, double p_cross, double p_mut, int skip_init_draws, uint8_t* child_slot,
                 uint8_t* child_room, uint8_t* child_flags, void* stream);

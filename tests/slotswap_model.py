@@ -9,6 +9,12 @@ trade places:
                 pairs on one day, the last-slot term from the slots' weights;
   deltas_windows  deltas_table with the pairs on one day from co-occurrence
                 counts of the windows of three, as the kernel contracts them.
+  deltas_lut    the same deltas from a 512-entry table of h over the nine bits
+                of a day: D by table lookup and att^T . D as one float64
+                product (exact: its sums stay far below 2^53), the pairs on
+                one day from the count of each day pattern. Shares no step
+                with the kernel's contractions and takes milliseconds where
+                the other forms take seconds (S in the tens of thousands).
 descend() is the steepest descent with the header's tie rule."""
 import numpy as np
 
@@ -142,6 +148,39 @@ def deltas_windows(inst, slot):
     v = T + T.T - diag[:, None] - diag[None, :]
     for (a, b), same in same_day_windows(att).items():
         v[a, b] = same
+    last = (np.arange(SLOTS) % PER_DAY == PER_DAY - 1).astype(np.int64)
+    v = v + (W[None, :] - W[:, None]) * (last[:, None] - last[None, :])
+    return np.where(np.triu(np.ones((SLOTS, SLOTS), bool), k=1), v, NO_PAIR)
+
+
+def _day_tables():
+    """H[i] = h of the day whose bit k is position k of i; DL[i][k] = H[i | bit k]
+    - H[i & ~bit k]; SW[i][c] = H[i with the bits of pair c exchanged] - H[i]."""
+    i = np.arange(1 << PER_DAY)
+    H = day_cost(((i[:, None] >> np.arange(PER_DAY)) & 1).astype(bool))
+    DL = np.stack([H[i | (1 << k)] - H[i & ~(1 << k)] for k in range(PER_DAY)], axis=1)
+    pairs = [(ka, kb) for ka in range(PER_DAY) for kb in range(ka + 1, PER_DAY)]
+    SW = np.stack([H[np.where(((i >> ka) ^ (i >> kb)) & 1, i ^ ((1 << ka) | (1 << kb)), i)] - H for ka, kb in pairs],
+                  axis=1)
+    return DL, SW, pairs
+
+
+_DAY_TABLES = _day_tables()
+
+
+def deltas_lut(inst, slot):
+    DL, SW, pairs = _DAY_TABLES
+    att = attendance(inst, slot)
+    W = weights(inst, slot)
+    idx = att.reshape(-1, DAYS, PER_DAY).astype(np.int64) @ (1 << np.arange(PER_DAY))       # [S, 5]
+    D = DL[idx].reshape(-1, SLOTS)
+    T = np.rint(att.astype(np.float64).T @ D.astype(np.float64)).astype(np.int64)
+    diag = np.diagonal(T)
+    v = T + T.T - diag[:, None] - diag[None, :]
+    for d in range(DAYS):
+        same = np.bincount(idx[:, d], minlength=1 << PER_DAY).astype(np.int64) @ SW
+        for (ka, kb), dl in zip(pairs, same):
+            v[PER_DAY * d + ka, PER_DAY * d + kb] = dl
     last = (np.arange(SLOTS) % PER_DAY == PER_DAY - 1).astype(np.int64)
     v = v + (W[None, :] - W[:, None]) * (last[:, None] - last[None, :])
     return np.where(np.triu(np.ones((SLOTS, SLOTS), bool), k=1), v, NO_PAIR)

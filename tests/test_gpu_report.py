@@ -132,7 +132,7 @@ def test_parts_crowded_cell(orc):
 def test_parts_degenerate_instances(orc):
     one = ttga.Instance(1, 1, 1, 0, np.array([5], np.int32), np.zeros((0, 1), np.int32), np.ones((1, 1), np.int32),
                         np.zeros((1, 1), np.int32))
-    parts, eh = check_all(one, orc, np.array([[8]], np.uint8), np.zeros((1, 1), np.uint8), with_eval=False)
+    parts, eh = check_all(one, orc, np.array([[8]], np.uint8), np.zeros((1, 1), np.uint8))
     assert not parts.any() and not eh.any()
 
     # an event nobody attends (its correlation diagonal is 0) and a student with no events
