@@ -39,7 +39,15 @@ struct DevProblem {
     const int32_t* srun_part;     // run index range of each wave: [kSrunPart4 + w] for 4-wave,
                                   //   [kSrunPart8 + w] for 8-wave, [kSrunPart16 + w] for 16-wave groups
     int32_t* status;              // device status word (tt_device_status)
+    const uint8_t* t5_img;        // eval_tile5's lane-ready invariants (t5_img_bytes below,
+    int t5_img_bytes;             //   tt_internal.h); null and 0 when EW64 > 7
 };
+// eval_tile5's invariant image: EWC (EWC + 1) / 2 correlation rows of 64 u64, then the
+// per-event rows of the PK form (1: one u32 row per event word, 2: u32 + i32, 0: u64 + i32)
+__host__ __device__ constexpr int t5_img_corr_rows(int EWC) { return EWC * (EWC + 1) / 2; }
+__host__ __device__ constexpr int t5_img_bytes(int EWC, int PK) {
+    return 512 * t5_img_corr_rows(EWC) + EWC * (PK == 1 ? 256 : PK == 2 ? 512 : 768);
+}
 constexpr int kSrunPart4 = 0, kSrunPart8 = 5, kSrunPart16 = 14, kSrunPartLen = 32;
 __host__ __device__ constexpr int srun_part_base(int nw) { return nw == 4 ? kSrunPart4 : nw == 8 ? kSrunPart8 : kSrunPart16; }
 

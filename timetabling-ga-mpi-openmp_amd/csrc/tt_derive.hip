@@ -192,4 +192,41 @@ int derive_on_device(const tt_problem* p, const uint32_t* atb, const int32_t* ro
     return check_hip(he, "derive_on_device");
 }
 
+namespace {
+
+// eval_tile5's invariant image (layout: tt_internal.h): one 64-lane workgroup per
+// event word r writes the word's correlation rows (r, r..EWC-1) and its per-event
+// rows.
+__global__ __launch_bounds__(64) void t5_image_kernel(DevProblem d, int pk, uint8_t* img) {
+    const int E = d.E, EWC = d.EW64, r = blockIdx.x, lane = threadIdx.x;
+    const int e = 64 * r + lane;
+    const bool ok = e < E;
+    uint64_t* c = (uint64_t*)img + (size_t)(r * EWC - r * (r - 1) / 2) * 64 + lane;   // row (r, r)
+    for (int w = r; w < EWC; ++w) c[(w - r) * 64] = ok ? d.cupT[(size_t)w * E + e] : 0ull;
+    uint8_t* ev = img + 512 * t5_img_corr_rows(EWC);
+    const uint64_t poss = ok ? d.poss[e] : ~0ull;
+    const int32_t sn = ok ? d.sn[e] : 0;
+    if (pk == 1) {
+        ((uint32_t*)ev)[e] = ok ? ((~(uint32_t)poss & 0xFFFFu) | ((uint32_t)sn << 16)) : 0u;
+    } else if (pk == 2) {
+        ((uint32_t*)ev)[e] = (uint32_t)poss;
+        ((int32_t*)(ev + 256 * EWC))[e] = sn;
+    } else {
+        ((uint64_t*)ev)[e] = poss;
+        ((int32_t*)(ev + 512 * EWC))[e] = sn;
+    }
+}
+
+}  // namespace
+
+int build_t5_image(tt_problem* p) {
+    DevProblem& d = p->dev;
+    if (!d.t5_img) return TT_OK;
+    const int pk = t5_pk(p->R, p->max_sn);
+    d.t5_img_bytes = t5_img_bytes(d.EW64, pk);
+    hipLaunchKernelGGL(t5_image_kernel, dim3(d.EW64), dim3(64), 0, nullptr, d, pk, const_cast<uint8_t*>(d.t5_img));
+    TT_HIP(hipGetLastError());
+    return check_hip(hipStreamSynchronize(nullptr), "build_t5_image");
+}
+
 }  // namespace ttga

@@ -65,6 +65,19 @@ typedef __attribute__((address_space(3))) unsigned long long LdsU64;
 //    correlation read of that event's row carry the word index as the
 //    instruction's immediate offset, so the slot values are dead after the
 //    per-event block;
+//  * prologue: the launch invariants (those correlation words, possibleRooms and
+//    studentNumber of the lane's events) come from the problem's lane-ready image
+//    (DevProblem::t5_img, layout in tt_internal.h, built once per problem), never
+//    ahead of the first tile's staging loads. DB kernels issue the first tile's
+//    DMA into buffer 0 and the image's DMA into buffer 1 back to back (one copy
+//    per workgroup instead of one per wave), wait once, and every wave fills its
+//    registers from buffer 1 by unconditional LDS reads; a second barrier frees
+//    buffer 1 for the second tile's DMA (and its sentinel column, which the image
+//    covered, is written then). Both barriers are paid once per launch: the tile
+//    loop skips its own on the first tile. Where the image is larger than a tile
+//    buffer (E <= 8) and in the kernels that stage by vector copies, the same
+//    rows are read from global memory, coalesced and unconditional, behind the
+//    first tile's staging loads;
 //  * an individual with an invalid gene is detected from registers before any
 //    LDS work (its outputs are the -1 sentinels); the valid path has no
 //    per-event branches except on the last, partial event word;
@@ -389,6 +402,37 @@ __device__ __forceinline__ void tile_dma(const uint8_t* src, uint8_t* dst, int n
     }
 }
 
+// One wave's share of the invariant image (DevProblem::t5_img, a multiple of
+// 256 B) by the same LDS-DMA: piece k of 256 B lands at dst + 256 k.
+template <int NW>
+__device__ __forceinline__ void image_dma(const uint8_t* img, int bytes, uint8_t* dst, int wv, int lane) {
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)img, 0, bytes, 0x00020000);
+    for (int k = wv; k < (bytes >> 8); k += NW)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(dst + 256 * k), 4,
+                                                 4 * lane, 256 * k, 0, 0);
+}
+
+// The lane's launch invariants from the image at img (global memory, or its copy
+// in LDS): every read is unconditional, row base + lane; the rows' order is
+// tt_internal.h's.
+template <int EWC, int PK, typename PossT>
+__device__ __forceinline__ void t5_load_inv(const uint8_t* img, int lane, uint64_t (*cup)[EWC], uint32_t* ps,
+                                            PossT* poss, int* sn) {
+    const uint64_t* c = (const uint64_t*)img + lane;
+    const uint8_t* ev = img + 512 * t5_img_corr_rows(EWC);
+#pragma unroll
+    for (int r = 0; r < EWC; ++r) {
+#pragma unroll
+        for (int w = 0; w < EWC; ++w) cup[r][w] = w >= r ? c[64 * (r * EWC - r * (r - 1) / 2 + w - r)] : 0ull;
+        if constexpr (PK == 1) {
+            ps[r] = ((const uint32_t*)ev)[64 * r + lane];
+        } else {
+            poss[r] = ((const PossT*)ev)[64 * r + lane];
+            sn[r] = ((const int*)(ev + EWC * 64 * sizeof(PossT)))[64 * r + lane];
+        }
+    }
+}
+
 // Profiling build (-DTT_T5_STAMP, libttga_prof.so, tools/t5_stamps.py): per
 // workgroup, the constant-clock time (s_memrealtime, 100 MHz) when its wave 0
 // starts and when each of its waves ends, and the hardware slot it ran on
@@ -511,21 +555,13 @@ __global__ __launch_bounds__(64 * NW, 4) void eval_tile5_kernel(DevProblem pb, c
     PossT inv_poss[EWC];
     uint32_t inv_ps[EWC];
     int inv_sn[EWC];
-#pragma unroll
-    for (int r = 0; r < EWC; ++r) {
-        const int e = lane + 64 * r;
-        const bool ok = e < E;
-        if constexpr (PK == 1) {
-            // low half: the rooms NOT possible for e (one bfe gives the unsuitable-room
-            // term), high half: studentNumber (read by v_mad_u32_u16's op_sel)
-            inv_ps[r] = ok ? ((~(uint32_t)pb.poss[e] & 0xFFFFu) | ((uint32_t)pb.sn[e] << 16)) : 0u;
-        } else {
-            inv_poss[r] = ok ? (PossT)pb.poss[e] : (PossT)~0ull;
-            inv_sn[r] = ok ? pb.sn[e] : 0;
-        }
-#pragma unroll
-        for (int w = 0; w < EWC; ++w) inv_cup[r][w] = (w >= r && ok) ? pb.cupT[(size_t)w * E + e] : 0ull;
-    }
+    // The invariants come from the problem's lane-ready image (PK 1, inv_ps: low half
+    // the rooms NOT possible for the event -- one bfe gives the unsuitable-room term --
+    // high half studentNumber, read by v_mad_u32_u16's op_sel), behind the first tile's
+    // staging loads: through LDS (tile buffer 1, idle until the second tile's DMA)
+    // where the image fits there, else from global memory.
+    auto load_inv = [&](const uint8_t* img) { t5_load_inv<EWC, PK, PossT>(img, lane, inv_cup, inv_ps, inv_poss, inv_sn); };
+    const bool img_lds = DB && (size_t)pb.t5_img_bytes <= L.tile_bytes;
     const ConstI32* ptab = (const ConstI32*)pb.srun_part;
     const int pbase = srun_part_base(NW);
     const int r0 = ptab[pbase + wv], r1 = ptab[pbase + wv + 1];     // this wave's student runs
@@ -534,28 +570,26 @@ __global__ __launch_bounds__(64 * NW, 4) void eval_tile5_kernel(DevProblem pb, c
     const uint32_t qinv = ((1u << 20) + (uint32_t)qpr - 1) / (uint32_t)max(qpr, 1);
 
     if constexpr (DB) {
-        // sentinel columns of both buffers (the DMA writes columns < E only), then the first tile
-        if (threadIdx.x < 128) lds[(threadIdx.x >> 6) * L.tile_bytes + (threadIdx.x & 63) * SP + E] = 63;
+        // sentinel column of buffer 0 (the DMA writes columns < E only), then the first tile
+        // and, back to back with it, the image into buffer 1
+        if (threadIdx.x < 64) lds[threadIdx.x * SP + E] = 63;
         if (blockIdx.x < tiles)
             tile_dma<NW>(slot + (long)blockIdx.x * 64 * E, lds, (int)min(64L, (long)P - (long)blockIdx.x * 64), E, SP,
                          wv, lane);
-    }
-    int it = 0;
-    for (int tl = blockIdx.x; tl < tiles; tl += gridDim.x, ++it) {
-        const long p0 = (long)tl * 64;
-        const int np = (int)min((long)64, (long)P - p0);
-        const uint8_t* src = slot + p0 * E;
-        if constexpr (DB) {
-            tile = lds + (it & 1) * L.tile_bytes;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's DMAs of the tile
-            __syncthreads();                                       // everyone's; the other buffer is free
-            const int tn = tl + gridDim.x;
-            if (tn < tiles)
-                tile_dma<NW>(slot + (long)tn * 64 * E, lds + ((it + 1) & 1) * L.tile_bytes,
-                             (int)min(64L, (long)P - (long)tn * 64), E, SP, wv, lane);
+        if (img_lds) {
+            image_dma<NW>(pb.t5_img, pb.t5_img_bytes, lds + L.tile_bytes, wv, lane);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's DMAs of tile 0 and the image
+            __syncthreads();                                       // everyone's
+            load_inv(lds + L.tile_bytes);
+            __syncthreads();                                       // buffer 1 is free for the second tile
         } else {
-        __syncthreads();
-        // ---- stage the tile's slot rows (+ sentinel column E = slot 63)
+            load_inv(pb.t5_img);
+        }
+        // sentinel column of buffer 1, which the image covered
+        if (threadIdx.x < 64) lds[L.tile_bytes + threadIdx.x * SP + E] = 63;
+    }
+    // non-DB: the tile's slot rows by vector copies (+ sentinel column E = slot 63)
+    auto stage = [&](const uint8_t* src, int np) {
         if (wide) {
             const uint4* s16 = (const uint4*)src;
 #pragma unroll 2
@@ -572,7 +606,34 @@ __global__ __launch_bounds__(64 * NW, 4) void eval_tile5_kernel(DevProblem pb, c
                 for (int c = lane; c < E; c += 64) tile[r * SP + c] = src[(long)r * E + c];
         }
         if (threadIdx.x < 64) tile[threadIdx.x * SP + E] = 63;
-        __syncthreads();
+    };
+    if constexpr (!DB) {
+        // the first tile, then the invariants behind its staging loads
+        if (blockIdx.x < tiles)
+            stage(slot + (long)blockIdx.x * 64 * E, (int)min(64L, (long)P - (long)blockIdx.x * 64));
+        load_inv(pb.t5_img);
+    }
+    int it = 0;
+    for (int tl = blockIdx.x; tl < tiles; tl += gridDim.x, ++it) {
+        const long p0 = (long)tl * 64;
+        const int np = (int)min((long)64, (long)P - p0);
+        const uint8_t* src = slot + p0 * E;
+        if constexpr (DB) {
+            tile = lds + (it & 1) * L.tile_bytes;
+            if (!(img_lds && it == 0)) {                           // (the image's barriers served the first tile)
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMAs of the tile
+                __syncthreads();                                   // everyone's; the other buffer is free
+            }
+            const int tn = tl + gridDim.x;
+            if (tn < tiles)
+                tile_dma<NW>(slot + (long)tn * 64 * E, lds + ((it + 1) & 1) * L.tile_bytes,
+                             (int)min(64L, (long)P - (long)tn * 64), E, SP, wv, lane);
+        } else {
+            if (it > 0) {
+                __syncthreads();
+                stage(src, np);
+            }
+            __syncthreads();
         }
 
         // ---- lane phase (lane = individual): attendance masks of this wave's students
@@ -1244,8 +1305,7 @@ extern "C" int tt_eval_variant(const tt_problem* p, const uint8_t* slot, const u
             set_error("instance too large for the tile5 kernel");
             return TT_ERR_LIMIT;
         }
-        const int max_sn = p->max_sn;
-        const int pk = (R <= 16 && max_sn <= 0xFFFF) ? 1 : R <= 32 ? 2 : 0;
+        const int pk = t5_pk(R, p->max_sn);                  // the form of the problem's invariant image
         const int tiles = (P + 63) / 64;
         // workgroups per CU of the kernel with one or two tile buffers: asked once per
         // problem (the occupancy query costs host time on every launch otherwise)

@@ -101,4 +101,26 @@ inline DeriveLayout derive_layout(int E, int S) {
 int derive_on_device(const tt_problem* p, const uint32_t* atb, const int32_t* room_size, const uint64_t* efw,
                      const uint64_t* rfw, int FW);
 
+// eval_tile5's packing of possibleRooms and studentNumber (its PK template
+// argument), fixed per problem: 1 = one u32 per event (R <= 16 and every
+// studentNumber < 65536), 2 = u32 room mask (R <= 32), 0 = u64 room mask.
+inline int t5_pk(int R, int max_sn) { return (R <= 16 && max_sn <= 0xFFFF) ? 1 : R <= 32 ? 2 : 0; }
+
+// eval_tile5's invariant image (DevProblem::t5_img, EW64 <= 7 only): what every
+// lane of the kernel keeps in registers for a whole launch, laid out so that a
+// wave reads each register's 64 values as one contiguous row, with no bounds
+// test and no index arithmetic. EWC = EW64, e = 64 r + lane:
+//  * correlation rows, 512 B each, r-major then w (r <= w < EWC):
+//      row (r, w)[lane] = cupT[w * E + e], 0 for e >= E;
+//  * per-event rows of the problem's PK form (t5_pk), event word r = 0..EWC-1:
+//      PK 1: u32 rows   (~possibleRooms & 0xFFFF) | studentNumber << 16, 0 for e >= E;
+//      PK 2: u32 rows   possibleRooms (all ones for e >= E),
+//            then i32 rows studentNumber (0 for e >= E);
+//      PK 0: u64 rows   possibleRooms (all ones for e >= E), then i32 rows studentNumber.
+// t5_img_bytes(EWC, PK) bytes (16,128 at E = 400, R = 10), a multiple of 256. The
+// image lives in the handle's device block, is written once by build_t5_image
+// after derive_on_device (cupT, possibleRooms and studentNumber are
+// device-derived) and is immutable afterwards. Synchronous.
+int build_t5_image(tt_problem* p);
+
 }  // namespace ttga

@@ -177,6 +177,9 @@ int tt_problem_create(int E, int R, int F, int S, const int32_t* room_size, cons
         {sid.data(), sizeof(uint16_t) * sid.size(), 0},
         {srun_flat.data(), sizeof(int32_t) * srun_flat.size(), 0},
         {srun_part.data(), sizeof(int32_t) * srun_part.size(), 0},
+        // eval_tile5's invariant image (device-built; the largest PK form: the form
+        // depends on the derived studentNumber)
+        {nullptr, EW64 <= 7 ? (size_t)t5_img_bytes(EW64, 0) : 0, 0},
     };
     size_t total = 0;
     for (auto& q : parts) { q.off = total; total += (q.bytes + 255) & ~(size_t)255; }
@@ -213,6 +216,8 @@ int tt_problem_create(int E, int R, int F, int S, const int32_t* room_size, cons
     d.sid = (const uint32_t*)(base + parts[12].off);
     d.srun = (const int4*)(base + parts[13].off);
     d.srun_part = (const int32_t*)(base + parts[14].off);
+    d.t5_img = parts[15].bytes ? base + parts[15].off : nullptr;
+    d.t5_img_bytes = 0;
 
     // studentNumber, eventCorrelations (and its two other layouts) and
     // possibleRooms: the MFMA derivation (csrc/tt_derive.hip)
@@ -233,6 +238,7 @@ int tt_problem_create(int E, int R, int F, int S, const int32_t* room_size, cons
         set_error("tt_problem_create: device studentNumber differs from the attendance counts");
         rc = TT_ERR_DEVICE;
     }
+    if (rc == TT_OK) rc = build_t5_image(p);        // after the derivation: cupT, and max_sn picks its form
     (void)hipSetDevice(prev);
     if (rc != TT_OK) {
         (void)hipFree(p->dev_block);
