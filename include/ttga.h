@@ -32,8 +32,10 @@
  * ttga_report.h, ttga_unique.h, ttga_greedy.h (a greedy constructive
  * initial population, the counterpart of tt_random_init), ttga_kempe.h
  * (the Kempe-chain interchange, a move of a whole conflict component
- * between two timeslots) and ttga_slotswap.h (the timeslot-swap descent:
- * two whole timeslots trade their events while that lowers scv).
+ * between two timeslots), ttga_slotswap.h (the timeslot-swap descent: two
+ * whole timeslots trade their events while that lowers scv) and ttga_lahc.h
+ * (late-acceptance hill climbing over feasible rows: single-event moves that
+ * keep hcv 0, the best row seen comes back).
  */
 #ifndef TTGA_H
 #define TTGA_H
@@ -244,7 +246,9 @@ int tt_ga_replace(const tt_problem* p, uint8_t* pop_slot, uint8_t* pop_room, int
  *   bit 6 (64) ttga_kempe.h's tt_kempe_move left a row with a slot gene >= 45 or
  *              a room gene >= R untouched;
  *   bit 7 (128) ttga_slotswap.h's tt_slot_swap left a row with a slot gene >= 45
- *              untouched.
+ *              untouched;
+ *   bit 8 (256) ttga_lahc.h's tt_lahc left a row with a slot gene >= 45 or a room
+ *              gene >= R untouched.
  * Synchronises the device. */
 int tt_device_status(const tt_problem* p, int32_t* status);
 

@@ -12,7 +12,17 @@
 //   ttga-ga -i instance.tim [-s seed] [-p type] [-c children]
 //           [-p1 x -p2 y -p3 z] [--gpus G] [--islands K] [--pop N] [--generations n] [--rccl] [--stagger]
 //           [--report] [--unique] [--init random|greedy] [--kempe P] [--kempe-max-chain N]
-//           [--slot-swap N]
+//           [--slot-swap N] [--lahc N] [--lahc-history L] [--lahc-swap P]
+//
+// --lahc N: tt_lahc (include/ttga_lahc.h) with N steps, history L (--lahc-history,
+// default 500) and swap probability P (--lahc-swap, default 0.5) runs directly
+// behind every tt_local_search_eval, and behind tt_slot_swap when that is on, on
+// the same stream: on every sub-batch of children with the children's own
+// streams, on the members with the initial streams before the initial sort. Rows
+// that are feasible walk and come back as the best row of the walk, their scv
+// and penalty lowered in place. Each island then prints one {"lahc": {"accepted",
+// "gain", "improved", "rows", "searched"}} line after the slotSwap line
+// (ttga.islands prints the same). The default is 0: no call.
 //
 // --slot-swap N: tt_slot_swap (include/ttga_slotswap.h) with max_passes N runs
 // directly behind every tt_local_search_eval, on the same stream, and lowers
@@ -92,6 +102,7 @@
 #include "../../include/ttga_greedy.h"
 #include "../../include/ttga_kempe.h"
 #include "../../include/ttga_slotswap.h"
+#include "../../include/ttga_lahc.h"
 #include "../../include/ttga_unique.h"
 
 namespace {
@@ -130,6 +141,9 @@ struct Control {
     double kempe = 0.0;                           // --kempe: tt_kempe_move's probability (0: never called)
     int kempe_max_chain = 0;                      // --kempe-max-chain (0: no cap)
     int slot_swap = 0;                            // --slot-swap: tt_slot_swap's max_passes (0: never called)
+    int lahc = 0;                                 // --lahc: tt_lahc's steps (0: never called)
+    int lahc_history = 500;                       // --lahc-history
+    double lahc_swap = 0.5;                       // --lahc-swap
 };
 
 // Control::Control (Control.cpp:3-137) plus the --gpus/--pop/--generations extensions.
@@ -184,6 +198,30 @@ Control parse_control(int argc, char** argv) {
             std::exit(1);
         }
         c.slot_swap = (int)v;
+        args.erase(it, it + 2);
+    }
+    for (const char* k : {"--lahc", "--lahc-history"}) {
+        auto it = std::find(args.begin(), args.end(), k);
+        if (it == args.end()) continue;
+        const bool hist = std::string(k) == "--lahc-history";
+        char* end = nullptr;
+        const double v = it + 1 == args.end() ? -1.0 : std::strtod((it + 1)->c_str(), &end);
+        if (!(v >= (hist ? 1 : 0) && v == std::floor(v) && v <= INT_MAX) || !end || *end || (it + 1)->empty()) {
+            std::cerr << "Error: " << k << " must be " << (hist ? "a positive integer" : "a non-negative integer")
+                      << std::endl;
+            std::exit(1);
+        }
+        (hist ? c.lahc_history : c.lahc) = (int)v;
+        args.erase(it, it + 2);
+    }
+    if (auto it = std::find(args.begin(), args.end(), "--lahc-swap"); it != args.end()) {
+        char* end = nullptr;
+        const double v = it + 1 == args.end() ? -1.0 : std::strtod((it + 1)->c_str(), &end);
+        if (!(v >= 0.0 && v <= 1.0) || !end || *end || (it + 1)->empty()) {
+            std::cerr << "Error: --lahc-swap must be a probability in [0, 1]" << std::endl;
+            std::exit(1);
+        }
+        c.lahc_swap = v;
         args.erase(it, it + 2);
     }
     for (const char* k : {"--gpus", "--islands", "--pop", "--generations", "--children", "--stagger-parts"}) {
@@ -582,6 +620,14 @@ struct Island {
     int slot_swap = 0;
     int32_t* swap_log = nullptr;
     long swap_cap = 0, swap_used = 0;
+    // --lahc: tt_lahc behind every search (and timeslot swap); each call leaves its gains in
+    // the next n entries of lahc_log, its accepted counts lahc_cap further on and the rows'
+    // feasible flags in lahc_feas, read once at the end
+    int lahc = 0, lahc_history = 500;
+    double lahc_swap = 0.5;
+    int32_t* lahc_log = nullptr;
+    uint8_t* lahc_feas = nullptr;
+    long lahc_cap = 0, lahc_used = 0;
 
     size_t work_bytes(int n) const {
         return std::max<size_t>(unique ? tt_ga_unique_work_bytes(N, n, E) : tt_ga_work_bytes(N, E), 16);
@@ -617,6 +663,11 @@ struct Island {
         if (slot_swap > 0) {
             swap_cap = N + std::max(replacements / parts * C, 1L);     // the members + generations x children
             check_hip(hipMalloc(&swap_log, 2 * 4 * (size_t)swap_cap), "hipMalloc");
+        }
+        if (lahc > 0) {
+            lahc_cap = N + std::max(replacements / parts * C, 1L);     // the members + generations x children
+            check_hip(hipMalloc(&lahc_log, 2 * 4 * (size_t)lahc_cap), "hipMalloc");
+            check_hip(hipMalloc(&lahc_feas, (size_t)lahc_cap), "hipMalloc");
         }
         migrant_bytes = 2 * (size_t)E + 13;
         check_hip(hipMalloc(&send_best, migrant_bytes), "hipMalloc");
@@ -672,6 +723,7 @@ struct Island {
                                       pop.scv, pop.feasible, pop.penalty, st),
                  "tt_local_search_eval");
         if (slot_swap > 0) swap_slots(pop, st);
+        if (lahc > 0) late_acceptance(pop, rng_init, st);
         if (unique)
             check_tt(tt_ga_replace_unique(tp, pop.slot, pop.room, pop.hcv, pop.scv, pop.feasible, pop.penalty, N,
                                           pop.slot, pop.room, pop.hcv, pop.scv, pop.feasible, pop.penalty, 0, nullptr,
@@ -767,6 +819,46 @@ struct Island {
         return wrap("slotSwap", k);
     }
 
+    // --lahc: the late-acceptance walk of the searched rows r (streams g) on s, behind their
+    // search, evaluation and timeslot swap; their scv and penalty are lowered in place
+    void late_acceptance(const Pop& r, int64_t* g, hipStream_t s) {
+        if (lahc_used + r.n > lahc_cap) die("more late-acceptance rows than planned for");
+        check_tt(tt_lahc(tp, r.slot, r.room, g, r.n, lahc, lahc_history, lahc_swap, r.scv, r.penalty,
+                         lahc_log + lahc_used, lahc_log + lahc_cap + lahc_used, nullptr, s),
+                 "tt_lahc");
+        check_hip(hipMemcpyAsync(lahc_feas + lahc_used, r.feasible, (size_t)r.n, hipMemcpyDeviceToDevice, s),
+                  "hipMemcpyAsync");
+        lahc_used += r.n;
+    }
+
+    // the --lahc line (ttga/ga.py lahc_line)
+    Json lahc_report() {
+        flush();
+        std::vector<int32_t> gain(lahc_used), acc(lahc_used);
+        std::vector<uint8_t> feas(lahc_used);
+        for (const Part& p : part) check_hip(hipStreamSynchronize(p.s), "hipStreamSynchronize");
+        check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
+        if (lahc_used) {
+            check_hip(hipMemcpy(gain.data(), lahc_log, 4 * gain.size(), hipMemcpyDeviceToHost), "hipMemcpy");
+            check_hip(hipMemcpy(acc.data(), lahc_log + lahc_cap, 4 * acc.size(), hipMemcpyDeviceToHost), "hipMemcpy");
+            check_hip(hipMemcpy(feas.data(), lahc_feas, feas.size(), hipMemcpyDeviceToHost), "hipMemcpy");
+        }
+        long searched = 0, improved = 0, accepted = 0, total = 0;
+        for (long i = 0; i < lahc_used; i++) {
+            searched += feas[i] != 0;
+            improved += gain[i] > 0;
+            accepted += acc[i];
+            total += gain[i];
+        }
+        Json k;
+        k.obj["rows"] = Json::I(lahc_used);
+        k.obj["searched"] = Json::I(searched);
+        k.obj["improved"] = Json::I(improved);
+        k.obj["accepted"] = Json::I(accepted);
+        k.obj["gain"] = Json::I(total);
+        return wrap("lahc", k);
+    }
+
     // LPT order (C >= kLptMinChildren), localSearch and evaluation of rows [off, off + n) on s
     // (the search and the evaluation in one launch: ga.cpp:574-575)
     void search(int off, int n, hipStream_t s, void* w) {
@@ -839,6 +931,7 @@ struct Island {
         if (kempe > 0) kempe_move(p.off, p.n, p.s);
         search(p.off, p.n, p.s, p.work);
         if (slot_swap > 0) swap_slots(child_rows(p.off, p.n), p.s);
+        if (lahc > 0) late_acceptance(child_rows(p.off, p.n), rng_child + p.off, p.s);
         pending.push_back(j);
         if ((int)pending.size() >= parts) replace_oldest();
     }
@@ -952,7 +1045,7 @@ struct Island {
         child.release();
         for (void* p : {(void*)rng_init, (void*)rng_child, (void*)flags, (void*)order, (void*)send_best,
                         (void*)send_second, (void*)recv_buf, (void*)keep, (void*)kept_log, (void*)chain_log,
-                        (void*)swap_log})
+                        (void*)swap_log, (void*)lahc_log, (void*)lahc_feas})
             if (p) (void)hipFree(p);
         for (size_t j = 0; j < part.size(); j++) {
             if (part[j].work) (void)hipFree(part[j].work);
@@ -1015,6 +1108,9 @@ int main(int argc, char** argv) {
         I.kempe = ctl.kempe;
         I.kempe_max_chain = ctl.kempe_max_chain;
         I.slot_swap = ctl.slot_swap;
+        I.lahc = ctl.lahc;
+        I.lahc_history = ctl.lahc_history;
+        I.lahc_swap = ctl.lahc_swap;
     }
     std::vector<ncclComm_t> comms(K, nullptr);
     if (rccl) {
@@ -1146,6 +1242,11 @@ int main(int argc, char** argv) {
         for (int k = 0; k < K; k++) {
             check_hip(hipSetDevice(isl[k].device), "hipSetDevice");
             out.line(isl[k].slot_swap_report());
+        }
+    if (ctl.lahc > 0)
+        for (int k = 0; k < K; k++) {
+            check_hip(hipSetDevice(isl[k].device), "hipSetDevice");
+            out.line(isl[k].lahc_report());
         }
     if (ctl.report)
         for (int k = 0; k < K; k++) {

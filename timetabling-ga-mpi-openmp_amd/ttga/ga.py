@@ -19,6 +19,9 @@ kernels (include/ttga.h):
 * optionally (Island(slot_swap=N)) every searched row goes through the
   timeslot-swap descent (tt_slot_swap) before it is sorted in: an addition
   too, which changes scv only;
+* optionally (Island(lahc=N)) every searched row that is feasible then walks N
+  late-acceptance steps over feasible rows (tt_lahc) and comes back as the best
+  row of the walk: an addition too, which lowers scv only;
 * migration (ga.cpp:514-540) and the final MIN reduction (ga.cpp:234-257) are
   in ttga.islands.
 
@@ -218,13 +221,22 @@ class Island(Members):
     in place, so the replacement sorts on the true penalties with no second
     evaluation. It draws no random numbers. slot_swap=0 issues no call at all.
     slot_swap_stats() reports what the descents did.
+
+    lahc=n >= 1: tt_lahc(steps=n, history=lahc_history, p_swap=lahc_swap)
+    (include/ttga_lahc.h) runs on the part's stream directly behind every
+    tt_local_search_eval, and behind tt_slot_swap when that is on -- on the
+    children of a sub-batch, drawing from the children's own streams, and on
+    the members in initialize() before the sort, drawing from rng_init. Only
+    rows that are feasible walk; their scv and penalty tensors are lowered in
+    place. lahc=0 issues no call at all. lahc_stats() reports what the walks did.
     """
 
     def __init__(self, dp, pop_size: int = 10, children: int = 1, max_steps: int = 200, seed: int = 1,
                  p_cross: float = 0.8, p_mut: float = 0.5, skip_init_draws: bool = True, device=None,
                  p1: float = 1.0, p2: float = 1.0, p3: float = 0.0, lpt: bool | None = None, stream=None,
                  schedule: str = "batch", parts: int = 2, unique: bool = False, init: str = "random",
-                 kempe: float = 0.0, kempe_max_chain: int = 0, slot_swap: int = 0):
+                 kempe: float = 0.0, kempe_max_chain: int = 0, slot_swap: int = 0,
+                 lahc: int = 0, lahc_history: int = 500, lahc_swap: float = 0.5):
         """stream: a torch.cuda.Stream of the island's own, or None (torch's current
         stream). Islands multiplexed on one GPU (ttga.islands --islands K) each take
         one, so one island's launches fill the SIMD slots another's local-search tail
@@ -240,6 +252,12 @@ class Island(Members):
             raise ValueError("kempe_max_chain must be >= 0 (0: no cap)")
         if int(slot_swap) < 0:
             raise ValueError("slot_swap must be >= 0 (0: off)")
+        if int(lahc) < 0:
+            raise ValueError("lahc must be >= 0 (0: off)")
+        if int(lahc_history) < 1:
+            raise ValueError("lahc_history must be >= 1")
+        if not (0.0 <= float(lahc_swap) <= 1.0):
+            raise ValueError("lahc_swap must be a probability in [0, 1]")
         if not (1 <= children <= pop_size):
             raise ValueError("need 1 <= children <= pop_size")
         if schedule not in ("batch", "staggered"):
@@ -263,6 +281,7 @@ class Island(Members):
         self.init = init
         self.kempe, self.kempe_max_chain = float(kempe), int(kempe_max_chain)
         self.slot_swap = int(slot_swap)
+        self.lahc, self.lahc_history, self.lahc_swap = int(lahc), int(lahc_history), float(lahc_swap)
         self.generation = 0
         self.schedule = schedule
         self.parts = int(parts) if schedule == "staggered" else 1
@@ -320,6 +339,21 @@ class Island(Members):
                                                sums=torch.zeros(3, dtype=torch.int64, device=dev))
                 self._extra += list(vars(p.swap).values())
         self._swap_rows = 0
+        # lahc: each part's (and the members') gain, accepted and best_step and the running
+        # (rows searched, rows improved, accepted, gain), added up on the stream behind the
+        # call; the rows, on the host
+        if self.lahc > 0:
+            def lahc_buffers(n):
+                b = types.SimpleNamespace(gain=torch.zeros(n, dtype=torch.int32, device=dev),
+                                          accepted=torch.zeros(n, dtype=torch.int32, device=dev),
+                                          best_step=torch.zeros(n, dtype=torch.int32, device=dev),
+                                          sums=torch.zeros(4, dtype=torch.int64, device=dev))
+                self._extra += list(vars(b).values())
+                return b
+            self._lahc_init = lahc_buffers(self.N)
+            for p in self._parts:
+                p.lahc = lahc_buffers(p.n)
+        self._lahc_rows = 0
         self._replaced = 0
         self._pending = []                            # parts searched but not yet replaced, in breed order
         self._last_replace = 0                        # part whose work buffer holds the last replace's source
@@ -439,6 +473,8 @@ class Island(Members):
                                  out=(p["hcv"], p["scv"], p["feasible"], p["penalty"]))
             if self.slot_swap > 0:
                 self._slot_swap(p, self._swap_init)
+            if self.lahc > 0:
+                self._lahc(p, self.rng_init, self._lahc_init)
             if self.unique:
                 self.dp.ga_replace_unique(p, None, self.work, n_kept=self._init_kept)
             else:
@@ -485,6 +521,8 @@ class Island(Members):
             self._search(p.child, p.rng, p.work)
             if self.slot_swap > 0:
                 self._slot_swap(p.child, p.swap)
+            if self.lahc > 0:
+                self._lahc(p.child, p.rng, p.lahc)
             self._pending.append(j)
             if len(self._pending) >= self.parts:
                 self._replace_oldest()
@@ -506,6 +544,31 @@ class Island(Members):
                           passes=b.passes)
         b.sums += torch.stack([(b.passes > 0).sum(), b.passes.sum(), b.gain.sum()])
         self._swap_rows += int(rows["slot"].shape[0])
+
+    def _lahc(self, rows, rng, b):
+        """tt_lahc on the searched rows (on the current stream, behind their
+        search and evaluation) and its counts, summed on the device behind the
+        call. The rows that walk are the feasible ones: the call's own gate is
+        tt_eval's hcv."""
+        import torch
+        self.dp.lahc(rows["slot"], rows["room"], rng, self.lahc, self.lahc_history, self.lahc_swap, scv=rows["scv"],
+                     penalty=rows["penalty"], gain=b.gain, accepted=b.accepted, best_step=b.best_step)
+        b.sums += torch.stack([(rows["feasible"] != 0).sum(), (b.gain > 0).sum(), b.accepted.sum(), b.gain.sum()])
+        self._lahc_rows += int(rows["slot"].shape[0])
+
+    def lahc_stats(self) -> dict:
+        """Island(lahc > 0): the rows tt_lahc was called on, how many of them
+        were feasible at entry and walked, how many came back better, the
+        candidates accepted and the scv gained in all, as Python ints. Pending
+        sub-batches are replaced first; synchronises."""
+        if not self.lahc > 0:
+            raise ValueError("lahc_stats() needs Island(lahc > 0)")
+        self.flush()
+        self.sync()
+        searched, improved, accepted, gain = (int(v) for v in sum(b.sums.cpu() for b in [self._lahc_init]
+                                                                  + [p.lahc for p in self._parts]).tolist())
+        return {"rows": int(self._lahc_rows), "searched": searched, "improved": improved, "accepted": accepted,
+                "gain": gain}
 
     def slot_swap_stats(self) -> dict:
         """Island(slot_swap > 0): the rows tt_slot_swap was called on, how many
@@ -730,6 +793,11 @@ def slot_swap_line(stats: dict) -> str:
     return json_line({"slotSwap": {"gain": int(stats["gain"]), "improved": improved,
                                    "meanPasses": float(stats["passes"]) / improved if improved else 0.0,
                                    "rows": int(stats["rows"])}})
+
+
+def lahc_line(stats: dict) -> str:
+    """The drivers' --lahc line of one island: Island.lahc_stats()."""
+    return json_line({"lahc": {k: int(stats[k]) for k in ("accepted", "gain", "improved", "rows", "searched")}})
 
 
 def run_final_line(procs: int, threads: int, total_time: float) -> str:

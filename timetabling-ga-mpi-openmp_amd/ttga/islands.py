@@ -32,6 +32,12 @@ Reference correspondence:
   directly behind every local search, ttga.ga.Island(slot_swap=N); each island
   then prints a `slotSwap` line after the solution, kempe and unique lines:
   rows, rows improved, mean swaps per improved row, scv gained; 0: no call),
+  `--lahc N` / `--lahc-history L` (500) / `--lahc-swap P` (0.5) (tt_lahc,
+  include/ttga_lahc.h: N late-acceptance steps on every feasible row directly
+  behind its local search and timeslot swap, ttga.ga.Island(lahc=N,
+  lahc_history=L, lahc_swap=P); each island then prints a `lahc` line after
+  the slotSwap line: rows, rows searched, rows improved, candidates accepted,
+  scv gained; 0: no call),
   `--stagger` / `--stagger-parts P` (the children of a generation as 2 / P
   sub-batches on as many streams, each bred P - 1 sub-batches behind:
   ttga.ga.Island's staggered schedule),
@@ -114,6 +120,30 @@ def parse_control(argv, out=sys.stdout, err=sys.stderr) -> dict:
             err.write("Error: --slot-swap must be a non-negative integer\n")
             raise SystemExit(1)
         extra["slot_swap"] = v
+        del args[i:i + 2]
+    for flag, key, low, what in (("--lahc", "lahc", 0, "a non-negative integer"),
+                                 ("--lahc-history", "lahc_history", 1, "a positive integer")):   # include/ttga_lahc.h
+        if flag in args:
+            i = args.index(flag)
+            try:
+                v = int(args[i + 1])
+            except (IndexError, ValueError):
+                v = -1
+            if not low <= v <= 2 ** 31 - 1:
+                err.write(f"Error: {flag} must be {what}\n")
+                raise SystemExit(1)
+            extra[key] = v
+            del args[i:i + 2]
+    if "--lahc-swap" in args:
+        i = args.index("--lahc-swap")
+        try:
+            v = float(args[i + 1])
+        except (IndexError, ValueError):
+            v = -1.0
+        if not 0.0 <= v <= 1.0:             # a NaN fails
+            err.write("Error: --lahc-swap must be a probability in [0, 1]\n")
+            raise SystemExit(1)
+        extra["lahc_swap"] = v
         del args[i:i + 2]
     if len(args) % 2 != 0:
         err.write("Parse error: Number of command line parameters incorrect\nUsage:\n" + USAGE + "\n")
@@ -256,7 +286,7 @@ def main(argv=None):
     import torch.distributed as dist
 
     from . import instance as tim
-    from .ga import (CostLog, Island, kempe_line, max_steps_for, run_best_line, run_final_line, slot_swap_line,
+    from .ga import (CostLog, Island, kempe_line, lahc_line, max_steps_for, run_best_line, run_final_line, slot_swap_line,
                      solution_line, unique_line)
 
     from .native import DeviceProblem
@@ -311,7 +341,8 @@ def main(argv=None):
                       stream=streams[k], schedule="staggered" if parts >= 2 else "batch", parts=max(parts, 2),
                       unique=bool(ctl.get("unique")), init=ctl.get("init", "random"),
                       kempe=ctl.get("kempe", 0.0), kempe_max_chain=ctl.get("kempe_max_chain", 0),
-                      slot_swap=ctl.get("slot_swap", 0))
+                      slot_swap=ctl.get("slot_swap", 0), lahc=ctl.get("lahc", 0),
+                      lahc_history=ctl.get("lahc_history", 500), lahc_swap=ctl.get("lahc_swap", 0.5))
                for k in range(K)]
     if rank == 0:
         islands[0].initialize()
@@ -365,6 +396,9 @@ def main(argv=None):
     if ctl.get("slot_swap", 0) > 0:
         for isl in islands:
             out.write(slot_swap_line(isl.slot_swap_stats()) + "\n")
+    if ctl.get("lahc", 0) > 0:
+        for isl in islands:
+            out.write(lahc_line(isl.lahc_stats()) + "\n")
     if ctl.get("report"):
         from .report import report_line
         for k, isl in enumerate(islands):

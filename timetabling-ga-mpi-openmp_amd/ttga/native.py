@@ -43,6 +43,9 @@ KEMPE_EXPORTS = ("tt_kempe_move",)
 # include/ttga_slotswap.h
 SLOTSWAP_EXPORTS = ("tt_slot_swap",)
 
+# include/ttga_lahc.h
+LAHC_EXPORTS = ("tt_lahc",)
+
 _lib = None
 
 
@@ -112,6 +115,8 @@ def load(path: os.PathLike | str | None = None) -> ctypes.CDLL:
     lib.tt_kempe_move.restype = ctypes.c_int
     lib.tt_slot_swap.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.tt_slot_swap.restype = ctypes.c_int
+    lib.tt_lahc.argtypes = [vp, vp, vp, vp, i32, i32, i32, dbl, vp, vp, vp, vp, vp, vp]
+    lib.tt_lahc.restype = ctypes.c_int
     for name in EXPORTS:
         if name not in ("tt_last_error", "tt_ga_work_bytes", "tt_ga_work_source_offset"):
             getattr(lib, name).restype = ctypes.c_int
@@ -476,6 +481,27 @@ class DeviceProblem:
         ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)    # noqa: E731
         _check(self.lib, self.lib.tt_slot_swap(self.handle, slot.data_ptr(), P, int(max_passes), ptr(scv), ptr(penalty),
                                                ptr(gain), ptr(passes), ptr(perm), self._stream(slot)))
+
+    # -- late-acceptance search on feasible rows (include/ttga_lahc.h) -----------------
+    def lahc(self, slot, room, rng, steps, history, p_swap=0.5, scv=None, penalty=None, gain=None, accepted=None,
+             best_step=None):
+        """tt_lahc in place on slot, room [P, E] and rng [P]: per feasible row, a
+        walk of `steps` Move1 / Move2 candidates that keep hcv 0, accepted when
+        no worse than the current row or the one `history` steps ago; the best
+        row seen comes back. scv, penalty (int32 [P], updated in place), gain,
+        accepted and best_step (int32 [P]) are optional CUDA tensors."""
+        import torch
+        P = self._pop(slot, room)
+        self._rng(rng, P)
+        for name, t in (("scv", scv), ("penalty", penalty), ("gain", gain), ("accepted", accepted),
+                        ("best_step", best_step)):
+            if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == P
+                                      and t.device == slot.device):
+                raise ValueError(f"{name} must be a contiguous int32 CUDA tensor of P entries on the population's device")
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)    # noqa: E731
+        _check(self.lib, self.lib.tt_lahc(self.handle, slot.data_ptr(), room.data_ptr(), rng.data_ptr(), P, int(steps),
+                                          int(history), float(p_swap), ptr(scv), ptr(penalty), ptr(gain),
+                                          ptr(accepted), ptr(best_step), self._stream(slot)))
 
     @staticmethod
     def _rng(rng, P):

@@ -26,7 +26,7 @@ slots, rooms, hcv, scv, feasible, penalty and final RNG states
                              [--gens 3] [--steps 200] [--cpu-sample 512]
                              [--warm-gens N] [--warm-feasible F] [--unique]
                              [--init random|greedy] [--kempe P] [--kempe-max-chain N]
-                             [--slot-swap N]
+                             [--slot-swap N] [--lahc N] [--lahc-history L] [--lahc-swap P]
 
 --warm-gens / --warm-feasible run untimed generations first, until a fraction F
 of the population is feasible (or N generations), so the timed generations
@@ -47,6 +47,11 @@ chain moved, so the two runs' times are not like for like.
 with max_passes N behind every search; the record then carries "slot_swap" (N,
 the rows, the rows improved, the mean swaps per improved row and the scv
 gained). Its populations part from the plain run's at the first swap applied.
+--lahc N runs Island(lahc=N, lahc_history=L, lahc_swap=P): tt_lahc
+(include/ttga_lahc.h) with N steps behind every search; the record then
+carries "lahc" (N, L, P, the rows, the rows searched and improved, the
+candidates accepted and the scv gained). Its populations part from the plain
+run's at the first row that comes back better.
 """
 import argparse
 import json
@@ -105,6 +110,10 @@ def parser():
     ap.add_argument("--kempe-max-chain", type=int, default=0, help="the cap on a chain's length (0: none)")
     ap.add_argument("--slot-swap", type=int, default=0,
                     help="max_passes of tt_slot_swap behind every search (Island(slot_swap=...)); 0: never called")
+    ap.add_argument("--lahc", type=int, default=0,
+                    help="steps of tt_lahc behind every search (Island(lahc=...)); 0: never called")
+    ap.add_argument("--lahc-history", type=int, default=500, help="tt_lahc's history length")
+    ap.add_argument("--lahc-swap", type=float, default=0.5, help="tt_lahc's share of Move2 candidates")
     return ap
 
 
@@ -118,7 +127,8 @@ def run_ga(a):
     isls = [Island(dp, pop_size=a.pop, children=a.children, max_steps=a.steps, seed=seeds[k],
                    lpt=None if a.lpt == "auto" else a.lpt == "on", stream=torch.cuda.Stream() if K > 1 else None,
                    schedule=a.schedule, parts=a.parts, unique=a.unique, init=a.init, kempe=a.kempe,
-                   kempe_max_chain=a.kempe_max_chain, slot_swap=a.slot_swap)
+                   kempe_max_chain=a.kempe_max_chain, slot_swap=a.slot_swap, lahc=a.lahc,
+                   lahc_history=a.lahc_history, lahc_swap=a.lahc_swap)
             for k in range(K)]
     isl = isls[0]
     torch.cuda.synchronize()
@@ -199,8 +209,12 @@ def run_ga(a):
         k = {key: sum(s[key] for s in stats) for key in ("rows", "improved", "passes", "gain")}
         out["slot_swap"] = {"max_passes": a.slot_swap, "rows": k["rows"], "improved": k["improved"], "gain": k["gain"],
                             "mean_passes": k["passes"] / k["improved"] if k["improved"] else 0.0}
+    if a.lahc > 0:
+        stats = [i.lahc_stats() for i in isls]
+        out["lahc"] = {"steps": a.lahc, "history": a.lahc_history, "p_swap": a.lahc_swap,
+                       **{key: sum(s[key] for s in stats) for key in ("rows", "searched", "improved", "accepted", "gain")}}
     R = ref()
-    if R is not None and a.cpu_sample > 0 and not a.kempe > 0 and not a.slot_swap > 0:
+    if R is not None and a.cpu_sample > 0 and not a.kempe > 0 and not a.slot_swap > 0 and not a.lahc > 0:
         n = min(a.cpu_sample, a.children)
         threads, total, model = host_cores()
         h = R.problem(inst)

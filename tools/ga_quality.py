@@ -43,6 +43,14 @@ against the plain island, same seeds and parameters, no reference run: final
 values (Mann-Whitney U, two-sided), their medians, the medians of the logged
 best at generation checkpoints, and per run the rows, the rows improved, the
 swaps applied and the scv gained.
+
+--lahc N (with --lahc-history L, --lahc-swap P) does the same for the
+late-acceptance search: Island(lahc=N, lahc_history=L, lahc_swap=P) (tt_lahc,
+include/ttga_lahc.h, N steps behind every search) against the island without
+it, same seeds and parameters, no reference run; per run the rows, the rows
+searched and improved, the candidates accepted and the scv gained. Together
+with --slot-swap M both islands run Island(slot_swap=M) and only the lahc
+differs.
 """
 import argparse
 import json
@@ -72,7 +80,8 @@ def summarize(final, feas, trace, checkpoints):
 
 
 def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch", unique=False, stats_out=None,
-                init="random", kempe=0.0, kempe_max_chain=0, slot_swap=0):
+                init="random", kempe=0.0, kempe_max_chain=0, slot_swap=0, lahc=0, lahc_history=500,
+                lahc_swap=0.5):
     import torch
 
     from ttga import native
@@ -85,7 +94,7 @@ def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch", uni
     for k, s in enumerate(seeds):
         isl = Island(dp, pop_size=pop, children=children, max_steps=steps, seed=int(s), schedule=schedule,
                      unique=unique, init=init, kempe=kempe, kempe_max_chain=kempe_max_chain,
-                     slot_swap=slot_swap)
+                     slot_swap=slot_swap, lahc=lahc, lahc_history=lahc_history, lahc_swap=lahc_swap)
         tr = torch.zeros(gens + 1, dtype=torch.int64, device="cuda")
         p = isl.pop
 
@@ -108,7 +117,9 @@ def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch", uni
         feas[k] = 1 if isl.member_meta(0)[0] else 0
         final[k] = trace[k, -1]
         if stats_out is not None:
-            if slot_swap > 0:
+            if lahc > 0:
+                stats_out.append(isl.lahc_stats())
+            elif slot_swap > 0:
                 stats_out.append(isl.slot_swap_stats())
             elif kempe > 0:
                 stats_out.append(isl.kempe_stats())
@@ -143,6 +154,10 @@ def main():
     ap.add_argument("--kempe-max-chain", type=int, default=0, help="the cap on a chain's length (0: none)")
     ap.add_argument("--slot-swap", type=int, default=0,
                     help="N > 0: compare Island(slot_swap=N) with the plain island (no reference run)")
+    ap.add_argument("--lahc", type=int, default=0,
+                    help="N > 0: compare Island(lahc=N) with the island without it (no reference run)")
+    ap.add_argument("--lahc-history", type=int, default=500)
+    ap.add_argument("--lahc-swap", type=float, default=0.5)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     from scipy import stats
@@ -225,6 +240,31 @@ def main():
         res["tests"] = {"kempe_vs_plain": {
             "final_value_mannwhitney_p": 1.0 if same else float(stats.mannwhitneyu(vk, vp, alternative="two-sided").pvalue),
             "median_kempe": float(np.median(vk)), "median_plain": float(np.median(vp))}}
+        print(json.dumps(res), flush=True)
+        if a.out:
+            pathlib.Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
+        return
+    if a.lahc > 0:
+        dg = a.device_gens or a.gens
+        res["children_per_generation"], res["generations"] = a.device_children, dg
+        res["lahc"], res["lahc_history"], res["lahc_swap"], res["slot_swap"] = a.lahc, a.lahc_history, a.lahc_swap, a.slot_swap
+        cps = sorted({0, 1, 10, 100, dg // 2, dg} & set(range(dg + 1)))
+        for name, n in (("device", 0), ("device_lahc", a.lahc)):
+            st = [] if n > 0 else None
+            final, feas, trace, secs = device_runs(inst, seeds, a.pop, dg, a.steps, a.device_children,
+                                                   a.device_schedule, stats_out=st, slot_swap=a.slot_swap, lahc=n,
+                                                   lahc_history=a.lahc_history, lahc_swap=a.lahc_swap)
+            res["runs"][name] = summarize(final, feas, trace, cps)
+            res["runs"][name]["seconds_per_run"] = secs
+            if st:
+                res["runs"][name]["lahc_stats"] = st
+                res["runs"][name]["searched_share"] = sum(s["searched"] for s in st) / max(1, sum(s["rows"] for s in st))
+                res["runs"][name]["improved_share"] = sum(s["improved"] for s in st) / max(1, sum(s["rows"] for s in st))
+        vp, vs = (np.array(res["runs"][n]["final_log_value"]) for n in ("device", "device_lahc"))
+        same = bool(np.array_equal(vp, vs))
+        res["tests"] = {"lahc_vs_without": {
+            "final_value_mannwhitney_p": 1.0 if same else float(stats.mannwhitneyu(vs, vp, alternative="two-sided").pvalue),
+            "median_lahc": float(np.median(vs)), "median_without": float(np.median(vp))}}
         print(json.dumps(res), flush=True)
         if a.out:
             pathlib.Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
