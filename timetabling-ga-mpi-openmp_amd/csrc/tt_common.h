@@ -42,11 +42,23 @@ struct DevProblem {
     const uint8_t* t5_img;        // eval_tile5's lane-ready invariants (t5_img_bytes below,
     int t5_img_bytes;             //   tt_internal.h); null and 0 when EW64 > 7
 };
-// eval_tile5's invariant image: EWC (EWC + 1) / 2 correlation rows of 64 u64, then the
-// per-event rows of the PK form (1: one u32 row per event word, 2: u32 + i32, 0: u64 + i32)
-__host__ __device__ constexpr int t5_img_corr_rows(int EWC) { return EWC * (EWC + 1) / 2; }
-__host__ __device__ constexpr int t5_img_bytes(int EWC, int PK) {
-    return 512 * t5_img_corr_rows(EWC) + EWC * (PK == 1 ? 256 : PK == 2 ? 512 : 768);
+// eval_tile5's tail packing (its TP template argument), fixed per problem: with T <= 16
+// events in the last event word and at least one full word before it, the correlation
+// blocks (r, EWC-1) are evaluated from the tail events' side, TP = 4 of them per 64-lane
+// operation (lane l: tail event l & 15, block l >> 4); 1 = every block on its own.
+// (T <= 32 would admit TP = 2; no instance the project measures has such a tail, so only
+// 1 and 4 are instantiated.)
+__host__ __device__ constexpr int t5_tp(int E) { return (E > 64 && ((E - 1) & 63) < 16) ? 4 : 1; }
+__host__ __device__ constexpr int t5_packed_rows(int EWC, int TP) { return TP == 1 ? 0 : (EWC + TP - 1) / TP; }
+// eval_tile5's invariant image: the correlation rows of 64 u64 -- EWC (EWC + 1) / 2 of them
+// at TP 1; with a packed tail the upper triangle of the EWC - 1 full words, then the packed
+// rows --, then the per-event rows of the PK form (1: one u32 row per event word, 2: u32 +
+// i32, 0: u64 + i32)
+__host__ __device__ constexpr int t5_img_corr_rows(int EWC, int TP = 1) {
+    return TP == 1 ? EWC * (EWC + 1) / 2 : (EWC - 1) * EWC / 2 + t5_packed_rows(EWC, TP);
+}
+__host__ __device__ constexpr int t5_img_bytes(int EWC, int PK, int TP = 1) {
+    return 512 * t5_img_corr_rows(EWC, TP) + EWC * (PK == 1 ? 256 : PK == 2 ? 512 : 768);
 }
 constexpr int kSrunPart4 = 0, kSrunPart8 = 5, kSrunPart16 = 14, kSrunPartLen = 32;
 __host__ __device__ constexpr int srun_part_base(int nw) { return nw == 4 ? kSrunPart4 : nw == 8 ? kSrunPart8 : kSrunPart16; }

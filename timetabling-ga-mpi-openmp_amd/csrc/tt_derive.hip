@@ -196,14 +196,31 @@ namespace {
 
 // eval_tile5's invariant image (layout: tt_internal.h): one 64-lane workgroup per
 // event word r writes the word's correlation rows (r, r..EWC-1) and its per-event
-// rows.
-__global__ __launch_bounds__(64) void t5_image_kernel(DevProblem d, int pk, uint8_t* img) {
+// rows. With a packed tail (tp > 1) the triangle spans the EWC-1 full words, and
+// the last word's workgroup writes the packed rows instead: lane l holds, for tail
+// event j = 64 (EWC-1) + (l & (64/tp - 1)) and event word wd = l / (64/tp) + tp k,
+// the bits corr(j, 64 wd + i) -- a word of j's full correlation row (the pair is
+// counted from j's side, every i of a full word lies below j), or for wd = EWC-1
+// j's own upper-triangle word (i > j only).
+__global__ __launch_bounds__(64) void t5_image_kernel(DevProblem d, int pk, int tp, uint8_t* img) {
     const int E = d.E, EWC = d.EW64, r = blockIdx.x, lane = threadIdx.x;
     const int e = 64 * r + lane;
     const bool ok = e < E;
-    uint64_t* c = (uint64_t*)img + (size_t)(r * EWC - r * (r - 1) / 2) * 64 + lane;   // row (r, r)
-    for (int w = r; w < EWC; ++w) c[(w - r) * 64] = ok ? d.cupT[(size_t)w * E + e] : 0ull;
-    uint8_t* ev = img + 512 * t5_img_corr_rows(EWC);
+    const int F = tp == 1 ? EWC : EWC - 1;                      // words of the unpacked triangle
+    if (r < F) {
+        uint64_t* c = (uint64_t*)img + (size_t)(r * F - r * (r - 1) / 2) * 64 + lane;   // row (r, r)
+        for (int w = r; w < F; ++w) c[(w - r) * 64] = ok ? d.cupT[(size_t)w * E + e] : 0ull;
+    } else {
+        uint64_t* c = (uint64_t*)img + (size_t)(F * (F + 1) / 2) * 64 + lane;
+        const int per = 64 / tp, j = 64 * F + (lane & (per - 1));
+        for (int k = 0; k < t5_packed_rows(EWC, tp); ++k) {
+            const int wd = lane / per + tp * k;
+            c[k * 64] = (j >= E || wd > F) ? 0ull
+                        : wd == F          ? d.cupT[(size_t)F * E + j]
+                                           : d.corr64[(size_t)j * EWC + wd];
+        }
+    }
+    uint8_t* ev = img + 512 * t5_img_corr_rows(EWC, tp);
     const uint64_t poss = ok ? d.poss[e] : ~0ull;
     const int32_t sn = ok ? d.sn[e] : 0;
     if (pk == 1) {
@@ -223,8 +240,9 @@ int build_t5_image(tt_problem* p) {
     DevProblem& d = p->dev;
     if (!d.t5_img) return TT_OK;
     const int pk = t5_pk(p->R, p->max_sn);
-    d.t5_img_bytes = t5_img_bytes(d.EW64, pk);
-    hipLaunchKernelGGL(t5_image_kernel, dim3(d.EW64), dim3(64), 0, nullptr, d, pk, const_cast<uint8_t*>(d.t5_img));
+    const int tp = t5_tp(p->E);
+    d.t5_img_bytes = t5_img_bytes(d.EW64, pk, tp);
+    hipLaunchKernelGGL(t5_image_kernel, dim3(d.EW64), dim3(64), 0, nullptr, d, pk, tp, const_cast<uint8_t*>(d.t5_img));
     TT_HIP(hipGetLastError());
     return check_hip(hipStreamSynchronize(nullptr), "build_t5_image");
 }

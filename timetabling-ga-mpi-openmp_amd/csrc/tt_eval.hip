@@ -82,7 +82,12 @@ typedef __attribute__((address_space(3))) unsigned long long LdsU64;
 //    LDS work (its outputs are the -1 sentinels); the valid path has no
 //    per-event branches except on the last, partial event word;
 //  * PK: 1 = possibleRooms | studentNumber << 16 in one register (R <= 16,
-//    studentNumber < 65536), 2 = u32 mask (R <= 32), 0 = u64 mask.
+//    studentNumber < 65536), 2 = u32 mask (R <= 32), 0 = u64 mask;
+//  * TP: 4 = a last event word of at most 16 events behind at least one full word
+//    (t5_tp; E = 400: 16 events in word 6): its correlation blocks (r, EWC-1) are
+//    counted from the tail events' side, four event words per 64-lane operation
+//    (corr_words_tp), instead of one quarter-filled block each; 1 = every block on
+//    its own (corr_words).
 
 // acc + popcount(x) as two v_bcnt_u32_b32 with accumulate (no separate add).
 // (The compiler turns the plain form into bcnt, bcnt, add3.)
@@ -106,14 +111,18 @@ __device__ __forceinline__ uint32_t lds_addr(const void* p) {
 // ds_read2_b64), all in flight at once, with the wait in the same asm block, so
 // the results are defined when it ends: NA consecutive words from byte address
 // a + OA and NB from b + OB (NA + NB <= 8). OA and OB go into the instructions'
-// immediate offsets, so a and b can be row addresses that serve every word.
+// immediate offsets, so a and b can be row addresses that serve every word. A
+// third group rides in the same block: NC words from c + OC, SC bytes apart (the
+// packed tail reads of corr_words_tp).
 #define TT_O(k) [d##k] "=&v"(d[k])
-#define TT_I(k) [x##k] "v"(k < NA ? a : b), [o##k] "i"(k < NA ? OA + 8 * k : OB + 8 * (k - NA))
+#define TT_I(k)                                     \
+    [x##k] "v"(k < NA ? a : k < NA + NB ? b : c),   \
+        [o##k] "i"(k < NA ? OA + 8 * k : k < NA + NB ? OB + 8 * (k - NA) : OC + SC * (k - NA - NB))
 #define TT_R(k) "ds_read_b64 %[d" #k "], %[x" #k "] offset:%[o" #k "]\n"
-template <int NA, int NB, int OA, int OB>
-__device__ __forceinline__ void lds_two_rows(uint32_t a, uint32_t b, uint64_t* v) {
-    constexpr int N = NA + NB;
-    static_assert(NA >= 1 && NB >= 0 && N <= 8, "1..8 words");
+template <int NA, int NB, int OA, int OB, int NC = 0, int OC = 0, int SC = 0>
+__device__ __forceinline__ void lds_two_rows(uint32_t a, uint32_t b, uint64_t* v, uint32_t c = 0) {
+    constexpr int N = NA + NB + NC;
+    static_assert(NA >= 0 && NB >= 0 && NC >= 0 && N >= 1 && N <= 8, "1..8 words");
     uint64_t d[8];
     if constexpr (N == 8)
         asm volatile(TT_R(0) TT_R(1) TT_R(2) TT_R(3) TT_R(4) TT_R(5) TT_R(6) TT_R(7) "s_waitcnt lgkmcnt(0)"
@@ -170,6 +179,45 @@ __device__ __forceinline__ void corr_words(const uint32_t* row, const uint64_t (
         lds_two_rows<EWC - R, 0, 8 * R, 0>(row[R], row[R], bw);
 #pragma unroll
         for (int w = R; w < EWC; ++w) h = popc_acc(cup[R][w] & bw[w - R], h);
+    }
+}
+
+// The same with a packed tail (TP > 1, t5_tp): the F = EWC-1 full words keep the
+// scheme above among themselves (R paired with F-1-R), and the blocks (r, EWC-1),
+// the diagonal one included, are counted from the tail events' side instead:
+// #{i in word wd, j in the tail, corr_ij, slot_i == slot_j}
+//     = sum_j popcount(corr_row_j[wd] & B[slot_j][wd]),
+// TP words per 64-lane operation. Lane l serves tail event l & (64/TP - 1) and, in
+// packed operation k, word l / (64/TP) + TP k: prow is the lane's B-row address of
+// its tail event's slot with its first word's offset folded in, so operation k is
+// the immediate offset 8 TP k; pcup[k] is the image's packed row k (zero where the
+// lane has no tail event or no word: such a lane reads at most 8 (TP-1) bytes past
+// B's last row, into the wave's own cell counters). The packed reads ride in the
+// triangle's asm blocks while those have room (K placed so far); what is left goes
+// into one more block.
+template <int R, int EWC, int TP, int K = 0>
+__device__ __forceinline__ void corr_words_tp(const uint32_t* row, uint32_t prow, const uint64_t (*cup)[EWC],
+                                              const uint64_t* pcup, int& h) {
+    constexpr int F = EWC - 1, S = F - 1 - R, NPK = t5_packed_rows(EWC, TP);
+    if constexpr (R <= S) {
+        constexpr int NA = F - R, NB = R < S ? F - S : 0;
+        constexpr int NC = NPK - K < 8 - NA - NB ? NPK - K : 8 - NA - NB;
+        uint64_t bw[8];
+        lds_two_rows<NA, NB, 8 * R, 8 * S, NC, 8 * TP * K, 8 * TP>(row[R], row[S], bw, prow);
+#pragma unroll
+        for (int w = R; w < F; ++w) h = popc_acc(cup[R][w] & bw[w - R], h);
+        if constexpr (R < S) {
+#pragma unroll
+            for (int w = S; w < F; ++w) h = popc_acc(cup[S][w] & bw[NA + w - S], h);
+        }
+#pragma unroll
+        for (int k = 0; k < NC; ++k) h = popc_acc(pcup[K + k] & bw[NA + NB + k], h);
+        corr_words_tp<R + 1, EWC, TP, K + NC>(row, prow, cup, pcup, h);
+    } else if constexpr (K < NPK) {
+        uint64_t bw[8];
+        lds_two_rows<0, 0, 0, 0, NPK - K, 8 * TP * K, 8 * TP>(prow, prow, bw, prow);
+#pragma unroll
+        for (int k = K; k < NPK; ++k) h = popc_acc(pcup[k] & bw[k - K], h);
     }
 }
 
@@ -415,15 +463,18 @@ __device__ __forceinline__ void image_dma(const uint8_t* img, int bytes, uint8_t
 // The lane's launch invariants from the image at img (global memory, or its copy
 // in LDS): every read is unconditional, row base + lane; the rows' order is
 // tt_internal.h's.
-template <int EWC, int PK, typename PossT>
-__device__ __forceinline__ void t5_load_inv(const uint8_t* img, int lane, uint64_t (*cup)[EWC], uint32_t* ps,
-                                            PossT* poss, int* sn) {
+template <int EWC, int PK, int TP, typename PossT>
+__device__ __forceinline__ void t5_load_inv(const uint8_t* img, int lane, uint64_t (*cup)[EWC], uint64_t* pcup,
+                                            uint32_t* ps, PossT* poss, int* sn) {
+    constexpr int F = TP == 1 ? EWC : EWC - 1;          // words of the unpacked triangle
     const uint64_t* c = (const uint64_t*)img + lane;
-    const uint8_t* ev = img + 512 * t5_img_corr_rows(EWC);
+    const uint8_t* ev = img + 512 * t5_img_corr_rows(EWC, TP);
+#pragma unroll
+    for (int k = 0; k < t5_packed_rows(EWC, TP); ++k) pcup[k] = c[64 * (F * (F + 1) / 2 + k)];
 #pragma unroll
     for (int r = 0; r < EWC; ++r) {
 #pragma unroll
-        for (int w = 0; w < EWC; ++w) cup[r][w] = w >= r ? c[64 * (r * EWC - r * (r - 1) / 2 + w - r)] : 0ull;
+        for (int w = 0; w < EWC; ++w) cup[r][w] = (w >= r && w < F) ? c[64 * (r * F - r * (r - 1) / 2 + w - r)] : 0ull;
         if constexpr (PK == 1) {
             ps[r] = ((const uint32_t*)ev)[64 * r + lane];
         } else {
@@ -508,7 +559,7 @@ __device__ __forceinline__ void t5_clear_pieces(uint32_t m0v, uint32_t skip) {
 // (up to 8) wave-phase individuals nibble i of kT5PrioW
 constexpr int kT5PrioLane = 3;
 constexpr uint32_t kT5PrioW = 0x00112233u;
-template <int EWC, int NW, int PK, bool DB = false>
+template <int EWC, int NW, int PK, bool DB = false, int TP = 1>
 __global__ __launch_bounds__(64 * NW, 4) void eval_tile5_kernel(DevProblem pb, const uint8_t* __restrict__ slot,
                                                               const uint8_t* __restrict__ room, int P,
                                                               int32_t* __restrict__ hcv_out,
@@ -552,6 +603,7 @@ __global__ __launch_bounds__(64 * NW, 4) void eval_tile5_kernel(DevProblem pb, c
 
     using PossT = typename std::conditional<PK == 0, uint64_t, uint32_t>::type;
     uint64_t inv_cup[EWC][EWC];
+    uint64_t inv_pcup[TP == 1 ? 1 : t5_packed_rows(EWC, TP)];    // packed tail rows (corr_words_tp)
     PossT inv_poss[EWC];
     uint32_t inv_ps[EWC];
     int inv_sn[EWC];
@@ -560,7 +612,7 @@ __global__ __launch_bounds__(64 * NW, 4) void eval_tile5_kernel(DevProblem pb, c
     // high half studentNumber, read by v_mad_u32_u16's op_sel), behind the first tile's
     // staging loads: through LDS (tile buffer 1, idle until the second tile's DMA)
     // where the image fits there, else from global memory.
-    auto load_inv = [&](const uint8_t* img) { t5_load_inv<EWC, PK, PossT>(img, lane, inv_cup, inv_ps, inv_poss, inv_sn); };
+    auto load_inv = [&](const uint8_t* img) { t5_load_inv<EWC, PK, TP, PossT>(img, lane, inv_cup, inv_pcup, inv_ps, inv_poss, inv_sn); };
     const bool img_lds = DB && (size_t)pb.t5_img_bytes <= L.tile_bytes;
     const ConstI32* ptab = (const ConstI32*)pb.srun_part;
     const int pbase = srun_part_base(NW);
@@ -568,6 +620,11 @@ __global__ __launch_bounds__(64 * NW, 4) void eval_tile5_kernel(DevProblem pb, c
     const bool wide = (E & 15) == 0 && (((uintptr_t)slot) & 15) == 0;
     const int qpr = E >> 4;
     const uint32_t qinv = ((1u << 20) + (uint32_t)qpr - 1) / (uint32_t)max(qpr, 1);
+    // packed tail (TP > 1): the lane's tail event as a tile column (the first tail event's,
+    // against a zero packed word, where the lane has none) and word 0 of its first block in B
+    constexpr int TPL = 64 / TP;
+    const uint32_t tcol = 64 * (EWC - 1) + ((lane & (TPL - 1)) + 64 * (EWC - 1) < E ? (lane & (TPL - 1)) : 0);
+    const uint32_t pb0 = lds_addr(B) + 8 * (lane / TPL);
 
     if constexpr (DB) {
         // sentinel column of buffer 0 (the DMA writes columns < E only), then the first tile
@@ -675,6 +732,8 @@ __global__ __launch_bounds__(64 * NW, 4) void eval_tile5_kernel(DevProblem pb, c
 #pragma unroll
             for (int r = 0; r < EWC; ++r)
                 sv[r] = (!last_partial || r < EWC - 1 || lane + 64 * r < E) ? rs[lane + 64 * r] : 0u;
+            uint32_t ts = 0;                                          // slot of the lane's tail event
+            if constexpr (TP > 1) ts = rs[tcol];
             if (q + NW < nq) load_row(q + NW, pfn);                   // next individual
             // an invalid gene anywhere -> sentinel outputs; decided from registers
             uint32_t smax = 0, rmax = 0;
@@ -726,7 +785,10 @@ __global__ __launch_bounds__(64 * NW, 4) void eval_tile5_kernel(DevProblem pb, c
                 if (!(ablate & 4)) {
                     // B-row words by single ds_read_b64 (2 LDS cycles per 512 B, 64 banks),
                     // not the ds_read2_b64 pairs the compiler forms (8 cycles per 1 KiB, 32 banks)
-                    corr_words<0, EWC>(row, inv_cup, h);   // :151-153
+                    if constexpr (TP == 1)
+                        corr_words<0, EWC>(row, inv_cup, h);   // :151-153
+                    else
+                        corr_words_tp<0, EWC, TP>(row, pb0 + __umul24(ts, (uint32_t)(EWC * 8)), inv_cup, inv_pcup, h);
                 }
                 // one reduction of h << 16 | last when every lane's two parts are < 1024
                 // (so both 64-lane sums stay below 2^16), else two
@@ -1305,7 +1367,7 @@ extern "C" int tt_eval_variant(const tt_problem* p, const uint8_t* slot, const u
             set_error("instance too large for the tile5 kernel");
             return TT_ERR_LIMIT;
         }
-        const int pk = t5_pk(R, p->max_sn);                  // the form of the problem's invariant image
+        const int pk = t5_pk(R, p->max_sn), tp = t5_tp(E);   // the form of the problem's invariant image
         const int tiles = (P + 63) / 64;
         // workgroups per CU of the kernel with one or two tile buffers: asked once per
         // problem (the occupancy query costs host time on every launch otherwise)
@@ -1337,15 +1399,18 @@ extern "C" int tt_eval_variant(const tt_problem* p, const uint8_t* slot, const u
                                feasible, penalty, ablate);
             return TT_OK;
         };
-#define TT_T5U(EWC, NWV, PKV)                                                                                      \
+#define TT_T5U(EWC, NWV, PKV, TPV)                                                                                 \
     {                                                                                                              \
-        const bool db = db_ok && occupancy(eval_tile5_kernel<EWC, NWV, PKV, true>, L1.bytes, true) >=              \
-                                     occupancy(eval_tile5_kernel<EWC, NWV, PKV, false>, L0.bytes, false);          \
-        rc = db ? launch(eval_tile5_kernel<EWC, NWV, PKV, true>, L1.bytes, true)                                   \
-                : launch(eval_tile5_kernel<EWC, NWV, PKV, false>, L0.bytes, false);                                \
+        const bool db = db_ok && occupancy(eval_tile5_kernel<EWC, NWV, PKV, true, TPV>, L1.bytes, true) >=         \
+                                     occupancy(eval_tile5_kernel<EWC, NWV, PKV, false, TPV>, L0.bytes, false);     \
+        rc = db ? launch(eval_tile5_kernel<EWC, NWV, PKV, true, TPV>, L1.bytes, true)                              \
+                : launch(eval_tile5_kernel<EWC, NWV, PKV, false, TPV>, L0.bytes, false);                           \
     }
+// (the packed-tail forms exist from two event words up: t5_tp)
+#define TT_T5P(EWC, NWV, PKV) \
+    if (EWC > 1 && tp == 4) { TT_T5U(EWC, NWV, PKV, (EWC > 1 ? 4 : 1)) } else { TT_T5U(EWC, NWV, PKV, 1) }
 #define TT_T5N(EWC, NWV) \
-    if (pk == 1) { TT_T5U(EWC, NWV, 1) } else if (pk == 2) { TT_T5U(EWC, NWV, 2) } else { TT_T5U(EWC, NWV, 0) }
+    if (pk == 1) { TT_T5P(EWC, NWV, 1) } else if (pk == 2) { TT_T5P(EWC, NWV, 2) } else { TT_T5P(EWC, NWV, 0) }
 #define TT_T5(EWC)                                                      \
     case EWC:                                                           \
         if (NW == 4) { TT_T5N(EWC, 4) } else { TT_T5N(EWC, 8) }         \
@@ -1356,6 +1421,7 @@ extern "C" int tt_eval_variant(const tt_problem* p, const uint8_t* slot, const u
         }
 #undef TT_T5
 #undef TT_T5N
+#undef TT_T5P
 #undef TT_T5U
         if (rc) return rc;
     } else {

@@ -110,14 +110,21 @@ inline int t5_pk(int R, int max_sn) { return (R <= 16 && max_sn <= 0xFFFF) ? 1 :
 // lane of the kernel keeps in registers for a whole launch, laid out so that a
 // wave reads each register's 64 values as one contiguous row, with no bounds
 // test and no index arithmetic. EWC = EW64, e = 64 r + lane:
-//  * correlation rows, 512 B each, r-major then w (r <= w < EWC):
+//  * correlation rows, 512 B each, r-major then w (r <= w < F; F = EWC at TP 1,
+//    EWC - 1 with a packed tail, t5_tp in tt_common.h):
 //      row (r, w)[lane] = cupT[w * E + e], 0 for e >= E;
+//  * packed tail rows (TP > 1), 512 B each, k = 0..ceil(EWC/TP)-1, in place of the
+//    rows (r, EWC-1): with j = 64 (EWC-1) + (lane & (64/TP - 1)) and
+//    wd = lane / (64/TP) + TP k,
+//      row k[lane] bit i = corr(j, 64 wd + i) for wd < EWC-1,
+//                          corr(j, 64 wd + i) and i > j - 64 (EWC-1) for wd = EWC-1
+//                          (the diagonal block), 0 for j >= E or wd >= EWC;
 //  * per-event rows of the problem's PK form (t5_pk), event word r = 0..EWC-1:
 //      PK 1: u32 rows   (~possibleRooms & 0xFFFF) | studentNumber << 16, 0 for e >= E;
 //      PK 2: u32 rows   possibleRooms (all ones for e >= E),
 //            then i32 rows studentNumber (0 for e >= E);
 //      PK 0: u64 rows   possibleRooms (all ones for e >= E), then i32 rows studentNumber.
-// t5_img_bytes(EWC, PK) bytes (16,128 at E = 400, R = 10), a multiple of 256. The
+// t5_img_bytes(EWC, PK, TP) bytes (13,568 at E = 400, R = 10), a multiple of 256. The
 // image lives in the handle's device block, is written once by build_t5_image
 // after derive_on_device (cupT, possibleRooms and studentNumber are
 // device-derived) and is immutable afterwards. Synchronous.
