@@ -33,9 +33,11 @@
  * initial population, the counterpart of tt_random_init), ttga_kempe.h
  * (the Kempe-chain interchange, a move of a whole conflict component
  * between two timeslots), ttga_slotswap.h (the timeslot-swap descent: two
- * whole timeslots trade their events while that lowers scv) and ttga_lahc.h
+ * whole timeslots trade their events while that lowers scv), ttga_lahc.h
  * (late-acceptance hill climbing over feasible rows: single-event moves that
- * keep hcv 0, the best row seen comes back).
+ * keep hcv 0, the best row seen comes back) and ttga_cx.h (a conflict-guided
+ * crossover: each event takes the parent's slot that clashes less with what
+ * the child holds already, and a breed call built on it).
  */
 #ifndef TTGA_H
 #define TTGA_H
@@ -248,7 +250,9 @@ int tt_ga_replace(const tt_problem* p, uint8_t* pop_slot, uint8_t* pop_room, int
  *   bit 7 (128) ttga_slotswap.h's tt_slot_swap left a row with a slot gene >= 45
  *              untouched;
  *   bit 8 (256) ttga_lahc.h's tt_lahc left a row with a slot gene >= 45 or a room
- *              gene >= R untouched.
+ *              gene >= R untouched;
+ *   bit 9 (512) ttga_cx.h's tt_crossover_guided or tt_ga_breed_guided skipped an
+ *              order entry outside 0..E-1.
  * Synchronises the device. */
 int tt_device_status(const tt_problem* p, int32_t* status);
 

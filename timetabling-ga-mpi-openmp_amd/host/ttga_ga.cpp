@@ -13,6 +13,15 @@
 //           [-p1 x -p2 y -p3 z] [--gpus G] [--islands K] [--pop N] [--generations n] [--rccl] [--stagger]
 //           [--report] [--unique] [--init random|greedy] [--kempe P] [--kempe-max-chain N]
 //           [--slot-swap N] [--lahc N] [--lahc-history L] [--lahc-swap P]
+//           [--crossover uniform|guided] [--crossover-repair]
+//
+// --crossover guided: every sub-batch is bred by tt_ga_breed_guided
+// (include/ttga_cx.h) in place of tt_ga_breed, in tt_greedy_order's event order;
+// with --crossover-repair an event that clashes in both parents' slots goes to a
+// slot of least cost. Each island then prints one {"crossover": {"children",
+// "clean", "crossed", "meanCost", "repaired"}} line directly after its solution
+// line, before a kempe line (ttga.islands prints the same). The default is
+// uniform: no new call.
 //
 // --lahc N: tt_lahc (include/ttga_lahc.h) with N steps, history L (--lahc-history,
 // default 500) and swap probability P (--lahc-swap, default 0.5) runs directly
@@ -103,6 +112,7 @@
 #include "../../include/ttga_kempe.h"
 #include "../../include/ttga_slotswap.h"
 #include "../../include/ttga_lahc.h"
+#include "../../include/ttga_cx.h"
 #include "../../include/ttga_unique.h"
 
 namespace {
@@ -144,6 +154,8 @@ struct Control {
     int lahc = 0;                                 // --lahc: tt_lahc's steps (0: never called)
     int lahc_history = 500;                       // --lahc-history
     double lahc_swap = 0.5;                       // --lahc-swap
+    bool guided = false;                          // --crossover guided: tt_ga_breed_guided breeds
+    bool cx_repair = false;                       // --crossover-repair
 };
 
 // Control::Control (Control.cpp:3-137) plus the --gpus/--pop/--generations extensions.
@@ -223,6 +235,22 @@ Control parse_control(int argc, char** argv) {
         }
         c.lahc_swap = v;
         args.erase(it, it + 2);
+    }
+    if (auto it = std::find(args.begin(), args.end(), "--crossover-repair"); it != args.end()) {
+        c.cx_repair = true;
+        args.erase(it);
+    }
+    if (auto it = std::find(args.begin(), args.end(), "--crossover"); it != args.end()) {
+        if (it + 1 == args.end() || (*(it + 1) != "uniform" && *(it + 1) != "guided")) {
+            std::cerr << "Error: --crossover must be uniform or guided" << std::endl;
+            std::exit(1);
+        }
+        c.guided = *(it + 1) == "guided";
+        args.erase(it, it + 2);
+    }
+    if (c.cx_repair && !c.guided) {
+        std::cerr << "Error: --crossover-repair needs --crossover guided" << std::endl;
+        std::exit(1);
     }
     for (const char* k : {"--gpus", "--islands", "--pop", "--generations", "--children", "--stagger-parts"}) {
         auto it = std::find(args.begin(), args.end(), k);
@@ -628,6 +656,13 @@ struct Island {
     int32_t* lahc_log = nullptr;
     uint8_t* lahc_feas = nullptr;
     long lahc_cap = 0, lahc_used = 0;
+    // --crossover guided: tt_ga_breed_guided breeds, in the event order cx_order; each call
+    // leaves its costs in the next n entries of cx_log, its repaired counts cx_cap further on
+    // and the children's flags in cx_flags, read once at the end
+    bool guided = false, cx_repair = false;
+    int32_t *cx_order = nullptr, *cx_log = nullptr;
+    uint8_t* cx_flags = nullptr;
+    long cx_cap = 0, cx_used = 0;
 
     size_t work_bytes(int n) const {
         return std::max<size_t>(unique ? tt_ga_unique_work_bytes(N, n, E) : tt_ga_work_bytes(N, E), 16);
@@ -668,6 +703,17 @@ struct Island {
             lahc_cap = N + std::max(replacements / parts * C, 1L);     // the members + generations x children
             check_hip(hipMalloc(&lahc_log, 2 * 4 * (size_t)lahc_cap), "hipMalloc");
             check_hip(hipMalloc(&lahc_feas, (size_t)lahc_cap), "hipMalloc");
+        }
+        if (guided) {
+            cx_cap = std::max(replacements / parts * C, 1L);           // generations x children
+            check_hip(hipMalloc(&cx_log, 2 * 4 * (size_t)cx_cap), "hipMalloc");
+            check_hip(hipMalloc(&cx_flags, (size_t)cx_cap), "hipMalloc");
+            void* ev_work = nullptr;                                   // the order's scratch, needed once
+            check_hip(hipMalloc(&cx_order, 4 * (size_t)E), "hipMalloc");
+            check_hip(hipMalloc(&ev_work, tt_greedy_work_bytes(tp)), "hipMalloc");
+            check_tt(tt_greedy_order(tp, cx_order, ev_work, st), "tt_greedy_order");
+            check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
+            check_hip(hipFree(ev_work), "hipFree");
         }
         migrant_bytes = 2 * (size_t)E + 13;
         check_hip(hipMalloc(&send_best, migrant_bytes), "hipMalloc");
@@ -749,9 +795,49 @@ struct Island {
     // breed n children into rows [off, off + n) on stream s
     void breed(int off, int n, hipStream_t s) {
         Pop c = child_rows(off, n);
+        if (guided) {
+            if (cx_used + n > cx_cap) die("more guided crossovers than planned for");
+            check_tt(tt_ga_breed_guided(tp, pop.slot, pop.room, pop.penalty, N, cx_order, rng_child + off, n, p_cross,
+                                        p_mut, 1, cx_repair, c.slot, c.room, flags + off, cx_log + cx_used,
+                                        cx_log + cx_cap + cx_used, s),
+                     "tt_ga_breed_guided");
+            check_hip(hipMemcpyAsync(cx_flags + cx_used, flags + off, (size_t)n, hipMemcpyDeviceToDevice, s),
+                      "hipMemcpyAsync");
+            cx_used += n;
+            return;
+        }
         check_tt(tt_ga_breed(tp, pop.slot, pop.room, pop.penalty, N, rng_child + off, n, p_cross, p_mut, 1, c.slot,
                              c.room, flags + off, s),
                  "tt_ga_breed");
+    }
+
+    // the --crossover guided line (ttga/ga.py crossover_line)
+    Json crossover_report() {
+        flush();
+        std::vector<int32_t> cost(cx_used), rep(cx_used);
+        std::vector<uint8_t> fl(cx_used);
+        for (const Part& p : part) check_hip(hipStreamSynchronize(p.s), "hipStreamSynchronize");
+        check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
+        if (cx_used) {
+            check_hip(hipMemcpy(cost.data(), cx_log, 4 * cost.size(), hipMemcpyDeviceToHost), "hipMemcpy");
+            check_hip(hipMemcpy(rep.data(), cx_log + cx_cap, 4 * rep.size(), hipMemcpyDeviceToHost), "hipMemcpy");
+            check_hip(hipMemcpy(fl.data(), cx_flags, fl.size(), hipMemcpyDeviceToHost), "hipMemcpy");
+        }
+        long crossed = 0, clean = 0, total = 0, repaired = 0;
+        for (long i = 0; i < cx_used; i++) {
+            const bool x = (fl[i] & 1) != 0;
+            crossed += x;
+            clean += x && cost[i] == 0;
+            total += cost[i];
+            repaired += rep[i];
+        }
+        Json k;
+        k.obj["children"] = Json::I(cx_used);
+        k.obj["crossed"] = Json::I(crossed);
+        k.obj["clean"] = Json::I(clean);
+        k.obj["meanCost"] = Json::D(crossed ? (double)total / (double)crossed : 0.0);
+        k.obj["repaired"] = Json::I(repaired);
+        return wrap("crossover", k);
     }
 
     // --kempe: the Kempe-chain move on rows [off, off + n) on s, from the children's own streams
@@ -1045,7 +1131,8 @@ struct Island {
         child.release();
         for (void* p : {(void*)rng_init, (void*)rng_child, (void*)flags, (void*)order, (void*)send_best,
                         (void*)send_second, (void*)recv_buf, (void*)keep, (void*)kept_log, (void*)chain_log,
-                        (void*)swap_log, (void*)lahc_log, (void*)lahc_feas})
+                        (void*)swap_log, (void*)lahc_log, (void*)lahc_feas, (void*)cx_order, (void*)cx_log,
+                        (void*)cx_flags})
             if (p) (void)hipFree(p);
         for (size_t j = 0; j < part.size(); j++) {
             if (part[j].work) (void)hipFree(part[j].work);
@@ -1111,6 +1198,8 @@ int main(int argc, char** argv) {
         I.lahc = ctl.lahc;
         I.lahc_history = ctl.lahc_history;
         I.lahc_swap = ctl.lahc_swap;
+        I.guided = ctl.guided;
+        I.cx_repair = ctl.cx_repair;
     }
     std::vector<ncclComm_t> comms(K, nullptr);
     if (rccl) {
@@ -1231,6 +1320,7 @@ int main(int argc, char** argv) {
         check_hip(hipMemcpy(sl.data(), I.pop.slot, I.E, hipMemcpyDeviceToHost), "hipMemcpy");
         check_hip(hipMemcpy(rm.data(), I.pop.room, I.E, hipMemcpyDeviceToHost), "hipMemcpy");
         out.line(solution_line(b.feasible, b.scv, b.hcv, sl, rm, k, seconds_since(t_begin)));
+        if (ctl.guided) out.line(I.crossover_report());
         if (ctl.kempe > 0) out.line(I.kempe_report());
     }
     if (ctl.unique)

@@ -22,6 +22,10 @@ kernels (include/ttga.h):
 * optionally (Island(lahc=N)) every searched row that is feasible then walks N
   late-acceptance steps over feasible rows (tt_lahc) and comes back as the best
   row of the walk: an addition too, which lowers scv only;
+* optionally (Island(crossover="guided")) the children are bred with the
+  conflict-guided crossover (tt_ga_breed_guided) in place of the reference's
+  uniform one: an addition too, which changes only how a crossed child's
+  timeslots are chosen between its parents';
 * migration (ga.cpp:514-540) and the final MIN reduction (ga.cpp:234-257) are
   in ttga.islands.
 
@@ -229,6 +233,13 @@ class Island(Members):
     the members in initialize() before the sort, drawing from rng_init. Only
     rows that are feasible walk; their scv and penalty tensors are lowered in
     place. lahc=0 issues no call at all. lahc_stats() reports what the walks did.
+
+    crossover="guided": every sub-batch is bred with tt_ga_breed_guided
+    (include/ttga_cx.h) in place of tt_ga_breed, on the same stream and at the
+    same place in the operation chain, in the handle's greedy_order(); with
+    crossover_repair an event that clashes in both parents' slots goes to a
+    slot of least cost. Everything else is unchanged. crossover="uniform"
+    issues no new call at all. cx_stats() reports what the crossovers did.
     """
 
     def __init__(self, dp, pop_size: int = 10, children: int = 1, max_steps: int = 200, seed: int = 1,
@@ -236,7 +247,8 @@ class Island(Members):
                  p1: float = 1.0, p2: float = 1.0, p3: float = 0.0, lpt: bool | None = None, stream=None,
                  schedule: str = "batch", parts: int = 2, unique: bool = False, init: str = "random",
                  kempe: float = 0.0, kempe_max_chain: int = 0, slot_swap: int = 0,
-                 lahc: int = 0, lahc_history: int = 500, lahc_swap: float = 0.5):
+                 lahc: int = 0, lahc_history: int = 500, lahc_swap: float = 0.5,
+                 crossover: str = "uniform", crossover_repair: bool = False):
         """stream: a torch.cuda.Stream of the island's own, or None (torch's current
         stream). Islands multiplexed on one GPU (ttga.islands --islands K) each take
         one, so one island's launches fill the SIMD slots another's local-search tail
@@ -244,6 +256,10 @@ class Island(Members):
         synchronises its stream first, and a caller that moves data between islands
         (migration) synchronises the device around it."""
         import torch
+        if crossover not in ("uniform", "guided"):
+            raise ValueError("crossover must be 'uniform' or 'guided'")
+        if crossover_repair and crossover != "guided":
+            raise ValueError("crossover_repair needs crossover='guided'")
         if init not in ("random", "greedy"):
             raise ValueError("init must be 'random' or 'greedy'")
         if not (0.0 <= float(kempe) <= 1.0):
@@ -282,6 +298,7 @@ class Island(Members):
         self.kempe, self.kempe_max_chain = float(kempe), int(kempe_max_chain)
         self.slot_swap = int(slot_swap)
         self.lahc, self.lahc_history, self.lahc_swap = int(lahc), int(lahc_history), float(lahc_swap)
+        self.crossover, self.crossover_repair = crossover, bool(crossover_repair)
         self.generation = 0
         self.schedule = schedule
         self.parts = int(parts) if schedule == "staggered" else 1
@@ -354,6 +371,15 @@ class Island(Members):
             for p in self._parts:
                 p.lahc = lahc_buffers(p.n)
         self._lahc_rows = 0
+        # guided crossover: each part's cost and repaired and the running (crossed, clean, cost,
+        # repaired), added up on the part's stream behind the breed; the children, on the host
+        if self.crossover == "guided":
+            for p in self._parts:
+                p.cx = types.SimpleNamespace(cost=torch.zeros(p.n, dtype=torch.int32, device=dev),
+                                             repaired=torch.zeros(p.n, dtype=torch.int32, device=dev),
+                                             sums=torch.zeros(4, dtype=torch.int64, device=dev))
+                self._extra += list(vars(p.cx).values())
+        self._cx_children = 0
         self._replaced = 0
         self._pending = []                            # parts searched but not yet replaced, in breed order
         self._last_replace = 0                        # part whose work buffer holds the last replace's source
@@ -511,8 +537,11 @@ class Island(Members):
         p = self._parts[j]
         with self._on_stream(p.stream):
             self._wait_op(p.stream)                                         # breed(h) after replace(h - parts)
-            self.dp.ga_breed(self.pop["slot"], self.pop["room"], self.pop["penalty"], p.rng, p.child["slot"],
-                             p.child["room"], p.flags, self.p_cross, self.p_mut, self.skip)
+            if self.crossover == "guided":
+                self._breed_guided(p)
+            else:
+                self.dp.ga_breed(self.pop["slot"], self.pop["room"], self.pop["penalty"], p.rng, p.child["slot"],
+                                 p.child["room"], p.flags, self.p_cross, self.p_mut, self.skip)
             self._record_op(p.stream)
             if self._pending and len(self._pending) >= self.parts - 1:
                 self._replace_oldest()                                      # replace(h - parts + 1) after breed(h)
@@ -526,6 +555,31 @@ class Island(Members):
             self._pending.append(j)
             if len(self._pending) >= self.parts:
                 self._replace_oldest()
+
+    def _breed_guided(self, p):
+        """tt_ga_breed_guided for part p (on its stream, the current one) and
+        its counts, summed on the device behind the breed."""
+        import torch
+        b = p.cx
+        self.dp.ga_breed_guided(self.pop["slot"], self.pop["room"], self.pop["penalty"], p.rng, p.child["slot"],
+                                p.child["room"], p.flags, self.p_cross, self.p_mut, self.skip,
+                                repair=self.crossover_repair, cost=b.cost, repaired=b.repaired)
+        crossed = (p.flags & 1) != 0
+        b.sums += torch.stack([crossed.sum(), (crossed & (b.cost == 0)).sum(), b.cost.sum(), b.repaired.sum()])
+        self._cx_children += p.n
+
+    def cx_stats(self) -> dict:
+        """Island(crossover="guided"): the children bred, how many of them
+        crossed, how many of those came out with cost 0, and the cost and the
+        repaired events summed over the crossed children, as Python ints.
+        Pending sub-batches are replaced first; synchronises."""
+        if self.crossover != "guided":
+            raise ValueError("cx_stats() needs Island(crossover='guided')")
+        self.flush()
+        self.sync()
+        crossed, clean, cost, repaired = (int(v) for v in sum(p.cx.sums.cpu() for p in self._parts).tolist())
+        return {"children": int(self._cx_children), "crossed": crossed, "clean": clean, "cost": cost,
+                "repaired": repaired}
 
     def _kempe(self, p):
         """tt_kempe_move on the children of part p (on its stream, the current
@@ -798,6 +852,16 @@ def slot_swap_line(stats: dict) -> str:
 def lahc_line(stats: dict) -> str:
     """The drivers' --lahc line of one island: Island.lahc_stats()."""
     return json_line({"lahc": {k: int(stats[k]) for k in ("accepted", "gain", "improved", "rows", "searched")}})
+
+
+def crossover_line(stats: dict) -> str:
+    """The drivers' --crossover guided line of one island: Island.cx_stats()
+    with the mean cost of the crossed children (0 when none crossed)."""
+    crossed = int(stats["crossed"])
+    return json_line({"crossover": {"children": int(stats["children"]), "clean": int(stats["clean"]),
+                                    "crossed": crossed,
+                                    "meanCost": float(stats["cost"]) / crossed if crossed else 0.0,
+                                    "repaired": int(stats["repaired"])}})
 
 
 def run_final_line(procs: int, threads: int, total_time: float) -> str:

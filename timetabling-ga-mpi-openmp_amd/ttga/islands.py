@@ -38,6 +38,12 @@ Reference correspondence:
   lahc_history=L, lahc_swap=P); each island then prints a `lahc` line after
   the slotSwap line: rows, rows searched, rows improved, candidates accepted,
   scv gained; 0: no call),
+  `--crossover uniform|guided` / `--crossover-repair` (guided: the children are
+  bred by tt_ga_breed_guided, include/ttga_cx.h, ttga.ga.Island(crossover=
+  "guided", crossover_repair=...); each island then prints a `crossover` line
+  directly after its solution line, before a kempe line: children, crossed,
+  crossed children of cost 0, mean cost of the crossed, events repaired; the
+  default is uniform, which issues no new call),
   `--stagger` / `--stagger-parts P` (the children of a generation as 2 / P
   sub-batches on as many streams, each bred P - 1 sub-batches behind:
   ttga.ga.Island's staggered schedule),
@@ -145,6 +151,21 @@ def parse_control(argv, out=sys.stdout, err=sys.stderr) -> dict:
             raise SystemExit(1)
         extra["lahc_swap"] = v
         del args[i:i + 2]
+    repair = "--crossover-repair" in args   # include/ttga_cx.h
+    if repair:
+        args.remove("--crossover-repair")
+    if "--crossover" in args:
+        i = args.index("--crossover")
+        if i + 1 >= len(args) or args[i + 1] not in ("uniform", "guided"):
+            err.write("Error: --crossover must be uniform or guided\n")
+            raise SystemExit(1)
+        extra["crossover"] = args[i + 1]
+        del args[i:i + 2]
+    if repair:
+        if extra.get("crossover") != "guided":
+            err.write("Error: --crossover-repair needs --crossover guided\n")
+            raise SystemExit(1)
+        extra["crossover_repair"] = True
     if len(args) % 2 != 0:
         err.write("Parse error: Number of command line parameters incorrect\nUsage:\n" + USAGE + "\n")
         raise SystemExit(1)
@@ -286,7 +307,7 @@ def main(argv=None):
     import torch.distributed as dist
 
     from . import instance as tim
-    from .ga import (CostLog, Island, kempe_line, lahc_line, max_steps_for, run_best_line, run_final_line, slot_swap_line,
+    from .ga import (CostLog, Island, crossover_line, kempe_line, lahc_line, max_steps_for, run_best_line, run_final_line, slot_swap_line,
                      solution_line, unique_line)
 
     from .native import DeviceProblem
@@ -342,7 +363,8 @@ def main(argv=None):
                       unique=bool(ctl.get("unique")), init=ctl.get("init", "random"),
                       kempe=ctl.get("kempe", 0.0), kempe_max_chain=ctl.get("kempe_max_chain", 0),
                       slot_swap=ctl.get("slot_swap", 0), lahc=ctl.get("lahc", 0),
-                      lahc_history=ctl.get("lahc_history", 500), lahc_swap=ctl.get("lahc_swap", 0.5))
+                      lahc_history=ctl.get("lahc_history", 500), lahc_swap=ctl.get("lahc_swap", 0.5),
+                      crossover=ctl.get("crossover", "uniform"), crossover_repair=bool(ctl.get("crossover_repair")))
                for k in range(K)]
     if rank == 0:
         islands[0].initialize()
@@ -388,6 +410,8 @@ def main(argv=None):
         out.write(run_best_line(vals[0][0], gmin) + "\n")
     for k, isl in enumerate(islands):
         out.write(solution_line(isl.member(0), rank * K + k, time.perf_counter() - t_begin) + "\n")
+        if ctl.get("crossover") == "guided":
+            out.write(crossover_line(isl.cx_stats()) + "\n")
         if ctl.get("kempe", 0.0) > 0:
             out.write(kempe_line(isl.kempe_stats()) + "\n")
     if ctl.get("unique"):

@@ -46,6 +46,9 @@ SLOTSWAP_EXPORTS = ("tt_slot_swap",)
 # include/ttga_lahc.h
 LAHC_EXPORTS = ("tt_lahc",)
 
+# include/ttga_cx.h
+CX_EXPORTS = ("tt_crossover_guided", "tt_ga_breed_guided")
+
 _lib = None
 
 
@@ -117,6 +120,10 @@ def load(path: os.PathLike | str | None = None) -> ctypes.CDLL:
     lib.tt_slot_swap.restype = ctypes.c_int
     lib.tt_lahc.argtypes = [vp, vp, vp, vp, i32, i32, i32, dbl, vp, vp, vp, vp, vp, vp]
     lib.tt_lahc.restype = ctypes.c_int
+    lib.tt_crossover_guided.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]
+    lib.tt_crossover_guided.restype = ctypes.c_int
+    lib.tt_ga_breed_guided.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, dbl, dbl, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.tt_ga_breed_guided.restype = ctypes.c_int
     for name in EXPORTS:
         if name not in ("tt_last_error", "tt_ga_work_bytes", "tt_ga_work_source_offset"):
             getattr(lib, name).restype = ctypes.c_int
@@ -502,6 +509,53 @@ class DeviceProblem:
         _check(self.lib, self.lib.tt_lahc(self.handle, slot.data_ptr(), room.data_ptr(), rng.data_ptr(), P, int(steps),
                                           int(history), float(p_swap), ptr(scv), ptr(penalty), ptr(gain),
                                           ptr(accepted), ptr(best_step), self._stream(slot)))
+
+    # -- conflict-guided crossover (include/ttga_cx.h) -------------------------------
+    def _cx_args(self, slot, order, P, cost, repaired):
+        import torch
+        if order is None:
+            order = self.greedy_order()
+        elif not (order.is_cuda and order.dtype == torch.int32 and order.is_contiguous() and order.numel() == self.E
+                  and order.device == slot.device):
+            raise ValueError("order must be a contiguous int32 CUDA tensor of E entries on the population's device")
+        for name, t in (("cost", cost), ("repaired", repaired)):
+            if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == P
+                                      and t.device == slot.device):
+                raise ValueError(f"{name} must be a contiguous int32 CUDA tensor of P entries on the population's device")
+        return order
+
+    def crossover_guided(self, slot1, slot2, rng, slot, room, order=None, repair=False, cost=None, repaired=None):
+        """tt_crossover_guided: the counterpart of crossover; every event, in
+        `order` (int32 [E] CUDA tensor, default greedy_order()), takes the
+        parent's slot that clashes less with what the child holds already, the
+        coin between equals; with `repair` an event that clashes in both goes to
+        a slot of least cost. cost, repaired: optional int32 [P] CUDA tensors."""
+        P = self._pop(slot, room)
+        if self._pop(slot1, slot2) != P or slot2.shape[0] != P:
+            raise ValueError("the parents' tensors must have the children's shape [P, E]")
+        self._rng(rng, P)
+        order = self._cx_args(slot, order, P, cost, repaired)
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)    # noqa: E731
+        _check(self.lib, self.lib.tt_crossover_guided(self.handle, slot1.data_ptr(), slot2.data_ptr(),
+                                                      order.data_ptr(), rng.data_ptr(), slot.data_ptr(),
+                                                      room.data_ptr(), P, int(bool(repair)), ptr(cost), ptr(repaired),
+                                                      self._stream(slot)))
+
+    def ga_breed_guided(self, pop_slot, pop_room, pop_penalty, rng, child_slot, child_room, child_flags,
+                        p_cross=0.8, p_mut=0.5, skip_init_draws=True, order=None, repair=False, cost=None,
+                        repaired=None):
+        """tt_ga_breed_guided: ga_breed with the guided crossover (order, repair,
+        cost and repaired as in crossover_guided, over the C children)."""
+        N = self._pop(pop_slot, pop_room)
+        C = self._pop(child_slot, child_room)
+        self._rng(rng, C)
+        order = self._cx_args(child_slot, order, C, cost, repaired)
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)    # noqa: E731
+        _check(self.lib, self.lib.tt_ga_breed_guided(
+            self.handle, pop_slot.data_ptr(), pop_room.data_ptr(), pop_penalty.data_ptr(), N, order.data_ptr(),
+            rng.data_ptr(), C, float(p_cross), float(p_mut), int(bool(skip_init_draws)), int(bool(repair)),
+            child_slot.data_ptr(), child_room.data_ptr(), child_flags.data_ptr(), ptr(cost), ptr(repaired),
+            self._stream(pop_slot)))
 
     @staticmethod
     def _rng(rng, P):

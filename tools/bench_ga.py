@@ -27,6 +27,7 @@ slots, rooms, hcv, scv, feasible, penalty and final RNG states
                              [--warm-gens N] [--warm-feasible F] [--unique]
                              [--init random|greedy] [--kempe P] [--kempe-max-chain N]
                              [--slot-swap N] [--lahc N] [--lahc-history L] [--lahc-swap P]
+                             [--crossover uniform|guided] [--crossover-repair]
 
 --warm-gens / --warm-feasible run untimed generations first, until a fraction F
 of the population is feasible (or N generations), so the timed generations
@@ -52,6 +53,11 @@ gained). Its populations part from the plain run's at the first swap applied.
 carries "lahc" (N, L, P, the rows, the rows searched and improved, the
 candidates accepted and the scv gained). Its populations part from the plain
 run's at the first row that comes back better.
+--crossover guided runs Island(crossover="guided", crossover_repair=...):
+tt_ga_breed_guided (include/ttga_cx.h) breeds in place of tt_ga_breed; the
+record then carries "crossover" (the repair flag, the children, how many
+crossed, how many of those at cost 0, their mean cost and the events repaired).
+Its populations part from the plain run's at the first crossed child.
 """
 import argparse
 import json
@@ -114,6 +120,10 @@ def parser():
                     help="steps of tt_lahc behind every search (Island(lahc=...)); 0: never called")
     ap.add_argument("--lahc-history", type=int, default=500, help="tt_lahc's history length")
     ap.add_argument("--lahc-swap", type=float, default=0.5, help="tt_lahc's share of Move2 candidates")
+    ap.add_argument("--crossover", choices=["uniform", "guided"], default="uniform",
+                    help="the breeding operator: tt_ga_breed or tt_ga_breed_guided (Island(crossover=...))")
+    ap.add_argument("--crossover-repair", action="store_true",
+                    help="guided: an event that clashes in both parents' slots goes to a slot of least cost")
     return ap
 
 
@@ -128,7 +138,8 @@ def run_ga(a):
                    lpt=None if a.lpt == "auto" else a.lpt == "on", stream=torch.cuda.Stream() if K > 1 else None,
                    schedule=a.schedule, parts=a.parts, unique=a.unique, init=a.init, kempe=a.kempe,
                    kempe_max_chain=a.kempe_max_chain, slot_swap=a.slot_swap, lahc=a.lahc,
-                   lahc_history=a.lahc_history, lahc_swap=a.lahc_swap)
+                   lahc_history=a.lahc_history, lahc_swap=a.lahc_swap, crossover=a.crossover,
+                   crossover_repair=a.crossover_repair)
             for k in range(K)]
     isl = isls[0]
     torch.cuda.synchronize()
@@ -213,8 +224,15 @@ def run_ga(a):
         stats = [i.lahc_stats() for i in isls]
         out["lahc"] = {"steps": a.lahc, "history": a.lahc_history, "p_swap": a.lahc_swap,
                        **{key: sum(s[key] for s in stats) for key in ("rows", "searched", "improved", "accepted", "gain")}}
+    if a.crossover == "guided":
+        stats = [i.cx_stats() for i in isls]
+        k = {key: sum(s[key] for s in stats) for key in ("children", "crossed", "clean", "cost", "repaired")}
+        out["crossover"] = {"kind": "guided", "repair": bool(a.crossover_repair), "children": k["children"],
+                            "crossed": k["crossed"], "clean": k["clean"], "repaired": k["repaired"],
+                            "mean_cost": k["cost"] / k["crossed"] if k["crossed"] else 0.0}
     R = ref()
-    if R is not None and a.cpu_sample > 0 and not a.kempe > 0 and not a.slot_swap > 0 and not a.lahc > 0:
+    if (R is not None and a.cpu_sample > 0 and not a.kempe > 0 and not a.slot_swap > 0 and not a.lahc > 0
+            and a.crossover == "uniform"):
         n = min(a.cpu_sample, a.children)
         threads, total, model = host_cores()
         h = R.problem(inst)

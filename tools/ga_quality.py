@@ -51,6 +51,13 @@ it, same seeds and parameters, no reference run; per run the rows, the rows
 searched and improved, the candidates accepted and the scv gained. Together
 with --slot-swap M both islands run Island(slot_swap=M) and only the lahc
 differs.
+
+--crossover guided [--crossover-repair] does the same for the conflict-guided
+crossover: Island(crossover="guided", crossover_repair=...) (tt_ga_breed_guided,
+include/ttga_cx.h) against the island without it, same seeds and parameters, no
+reference run; per run the children, how many crossed, how many of those at
+cost 0, the cost and the events repaired. With --lahc N / --slot-swap M both
+islands run them and only the crossover differs.
 """
 import argparse
 import json
@@ -81,7 +88,7 @@ def summarize(final, feas, trace, checkpoints):
 
 def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch", unique=False, stats_out=None,
                 init="random", kempe=0.0, kempe_max_chain=0, slot_swap=0, lahc=0, lahc_history=500,
-                lahc_swap=0.5):
+                lahc_swap=0.5, crossover="uniform", crossover_repair=False):
     import torch
 
     from ttga import native
@@ -94,7 +101,8 @@ def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch", uni
     for k, s in enumerate(seeds):
         isl = Island(dp, pop_size=pop, children=children, max_steps=steps, seed=int(s), schedule=schedule,
                      unique=unique, init=init, kempe=kempe, kempe_max_chain=kempe_max_chain,
-                     slot_swap=slot_swap, lahc=lahc, lahc_history=lahc_history, lahc_swap=lahc_swap)
+                     slot_swap=slot_swap, lahc=lahc, lahc_history=lahc_history, lahc_swap=lahc_swap,
+                     crossover=crossover, crossover_repair=crossover_repair)
         tr = torch.zeros(gens + 1, dtype=torch.int64, device="cuda")
         p = isl.pop
 
@@ -117,7 +125,9 @@ def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch", uni
         feas[k] = 1 if isl.member_meta(0)[0] else 0
         final[k] = trace[k, -1]
         if stats_out is not None:
-            if lahc > 0:
+            if crossover == "guided":
+                stats_out.append(isl.cx_stats())
+            elif lahc > 0:
                 stats_out.append(isl.lahc_stats())
             elif slot_swap > 0:
                 stats_out.append(isl.slot_swap_stats())
@@ -158,6 +168,9 @@ def main():
                     help="N > 0: compare Island(lahc=N) with the island without it (no reference run)")
     ap.add_argument("--lahc-history", type=int, default=500)
     ap.add_argument("--lahc-swap", type=float, default=0.5)
+    ap.add_argument("--crossover", choices=["uniform", "guided"], default="uniform",
+                    help="guided: compare Island(crossover='guided') with the island without it (no reference run)")
+    ap.add_argument("--crossover-repair", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     from scipy import stats
@@ -179,6 +192,37 @@ def main():
     res = {"config": a.config, "E": inst.E, "R": inst.R, "F": inst.F, "S": inst.S, "pop_size": a.pop,
            "children_per_generation": 1, "generations": a.gens, "max_steps": a.steps, "seeds": seeds,
            "runs": {}}
+    if a.crossover_repair and a.crossover != "guided":
+        raise SystemExit("--crossover-repair needs --crossover guided")
+    if a.crossover == "guided":
+        dg = a.device_gens or a.gens
+        res["children_per_generation"], res["generations"] = a.device_children, dg
+        res["crossover"], res["crossover_repair"] = a.crossover, bool(a.crossover_repair)
+        res["lahc"], res["lahc_history"], res["lahc_swap"], res["slot_swap"] = a.lahc, a.lahc_history, a.lahc_swap, a.slot_swap
+        cps = sorted({0, 1, 10, 100, dg // 2, dg} & set(range(dg + 1)))
+        for name, cx in (("device", "uniform"), ("device_guided", "guided")):
+            st = [] if cx == "guided" else None
+            final, feas, trace, secs = device_runs(inst, seeds, a.pop, dg, a.steps, a.device_children,
+                                                   a.device_schedule, stats_out=st, slot_swap=a.slot_swap, lahc=a.lahc,
+                                                   lahc_history=a.lahc_history, lahc_swap=a.lahc_swap, crossover=cx,
+                                                   crossover_repair=a.crossover_repair and cx == "guided")
+            res["runs"][name] = summarize(final, feas, trace, cps)
+            res["runs"][name]["seconds_per_run"] = secs
+            if st:
+                res["runs"][name]["cx_stats"] = st
+                crossed = sum(s["crossed"] for s in st)
+                res["runs"][name]["clean_share"] = sum(s["clean"] for s in st) / max(1, crossed)
+                res["runs"][name]["mean_cost"] = sum(s["cost"] for s in st) / max(1, crossed)
+                res["runs"][name]["mean_repaired"] = sum(s["repaired"] for s in st) / max(1, crossed)
+        vp, vg = (np.array(res["runs"][n]["final_log_value"]) for n in ("device", "device_guided"))
+        same = bool(np.array_equal(vp, vg))
+        res["tests"] = {"guided_vs_uniform": {
+            "final_value_mannwhitney_p": 1.0 if same else float(stats.mannwhitneyu(vg, vp, alternative="two-sided").pvalue),
+            "median_guided": float(np.median(vg)), "median_uniform": float(np.median(vp))}}
+        print(json.dumps(res), flush=True)
+        if a.out:
+            pathlib.Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
+        return
     if a.unique:
         dg = a.device_gens or a.gens
         res["children_per_generation"], res["generations"] = a.device_children, dg
