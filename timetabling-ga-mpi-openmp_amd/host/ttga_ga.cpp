@@ -137,16 +137,9 @@ void check_nccl(ncclResult_t r, const char* what) {
 // ---------------------------------------------------------------- Control
 const char* kUsage = " -i InputFile [-o OutputFile] [-n NumberOfTries] [-s RandomSeed] [-t TimeLimit] [-p ProblemType]";
 
-struct Control {
-    int threads = 1, tries = 10, problem_type = 1, max_steps = 100;
-    double time_limit = 90, ls_limit = 99999, p1 = 1.0, p2 = 1.0, p3 = 0.0;
-    long seed = 0;
-    std::string input, output;
-    int gpus = 1, islands = 0, pop = 10, generations = -1;
-    bool rccl = false;
-    int stagger = 0;                              // sub-batches of the staggered schedule (0: batch)
-    bool report = false;                          // a population report line per island
-    bool unique = false;                          // duplicate-free replacement, a unique line per island
+// The optional stages' settings (ttga/stages.py lists the same flags)
+struct Stages {
+    bool unique = false;                          // --unique: duplicate-free replacement, a unique line per island
     bool greedy = false;                          // --init greedy: tt_greedy_init builds the initial population
     double kempe = 0.0;                           // --kempe: tt_kempe_move's probability (0: never called)
     int kempe_max_chain = 0;                      // --kempe-max-chain (0: no cap)
@@ -158,100 +151,95 @@ struct Control {
     bool cx_repair = false;                       // --crossover-repair
 };
 
+struct Control {
+    int threads = 1, tries = 10, problem_type = 1, max_steps = 100;
+    double time_limit = 90, ls_limit = 99999, p1 = 1.0, p2 = 1.0, p3 = 0.0;
+    long seed = 0;
+    std::string input, output;
+    int gpus = 1, islands = 0, pop = 10, generations = -1;
+    bool rccl = false;
+    int stagger = 0;                              // sub-batches of the staggered schedule (0: batch)
+    bool report = false;                          // a population report line per island
+    Stages stage;
+};
+
+// The extensions' flags are stripped from the arguments, with their values, before
+// Control.cpp's pair count; a missing or bad value prints the flag's message and exits with 1.
+using Args = std::vector<std::string>;
+
+[[noreturn]] void bad_flag(const char* msg) {
+    std::cerr << "Error: " << msg << std::endl;
+    std::exit(1);
+}
+
+// a bare flag: true when it was there
+bool take_flag(Args& args, const char* flag) {
+    auto it = std::find(args.begin(), args.end(), flag);
+    if (it == args.end()) return false;
+    args.erase(it);
+    return true;
+}
+
+// The word behind the flag at `it` as a number; a NaN, which fails every range check, where
+// there is none, where it is empty (unless empty_is_0: strtod's reading) or is not a number
+// to its last character
+double number_behind(const Args& args, Args::const_iterator it, bool empty_is_0) {
+    if (it + 1 == args.end() || ((it + 1)->empty() && !empty_is_0)) return NAN;
+    char* end = nullptr;
+    const double v = std::strtod((it + 1)->c_str(), &end);
+    return *end ? NAN : v;
+}
+
+// `flag N` with an integer N >= low
+void take_int(Args& args, const char* flag, int low, const char* msg, int& dst, bool empty_is_0 = false) {
+    auto it = std::find(args.begin(), args.end(), flag);
+    if (it == args.end()) return;
+    const double v = number_behind(args, it, empty_is_0);
+    if (!(v >= low && v == std::floor(v) && v <= INT_MAX)) bad_flag(msg);
+    dst = (int)v;
+    args.erase(it, it + 2);
+}
+
+// `flag P` with a probability P
+void take_prob(Args& args, const char* flag, const char* msg, double& dst, bool empty_is_0 = false) {
+    auto it = std::find(args.begin(), args.end(), flag);
+    if (it == args.end()) return;
+    const double v = number_behind(args, it, empty_is_0);
+    if (!(v >= 0.0 && v <= 1.0)) bad_flag(msg);
+    dst = v;
+    args.erase(it, it + 2);
+}
+
+// `flag first|second`: dst is whether it was the second word
+void take_choice(Args& args, const char* flag, const char* first, const char* second, const char* msg, bool& dst) {
+    auto it = std::find(args.begin(), args.end(), flag);
+    if (it == args.end()) return;
+    if (it + 1 == args.end() || (*(it + 1) != first && *(it + 1) != second)) bad_flag(msg);
+    dst = *(it + 1) == second;
+    args.erase(it, it + 2);
+}
+
 // Control::Control (Control.cpp:3-137) plus the --gpus/--pop/--generations extensions.
 Control parse_control(int argc, char** argv) {
-    std::vector<std::string> args(argv + 1, argv + argc);
+    Args args(argv + 1, argv + argc);
     Control c;
-    if (auto it = std::find(args.begin(), args.end(), "--rccl"); it != args.end()) {
-        c.rccl = true;
-        args.erase(it);
-    }
-    if (auto it = std::find(args.begin(), args.end(), "--stagger"); it != args.end()) {
-        c.stagger = 2;
-        args.erase(it);
-    }
-    if (auto it = std::find(args.begin(), args.end(), "--report"); it != args.end()) {
-        c.report = true;
-        args.erase(it);
-    }
-    if (auto it = std::find(args.begin(), args.end(), "--unique"); it != args.end()) {
-        c.unique = true;
-        args.erase(it);
-    }
-    if (auto it = std::find(args.begin(), args.end(), "--init"); it != args.end()) {
-        if (it + 1 == args.end() || (*(it + 1) != "random" && *(it + 1) != "greedy")) {
-            std::cerr << "Error: --init must be random or greedy" << std::endl;
-            std::exit(1);
-        }
-        c.greedy = *(it + 1) == "greedy";
-        args.erase(it, it + 2);
-    }
-    for (const char* k : {"--kempe", "--kempe-max-chain"}) {
-        auto it = std::find(args.begin(), args.end(), k);
-        if (it == args.end()) continue;
-        char* end = nullptr;
-        const bool prob = !std::strcmp(k, "--kempe");
-        const double v = it + 1 == args.end() ? -1.0 : std::strtod((it + 1)->c_str(), &end);
-        // an integer for the cap; a NaN fails both comparisons
-        if (!(v >= 0 && (prob ? v <= 1 : v == std::floor(v) && v <= INT_MAX)) || !end || *end) {
-            std::cerr << "Error: --kempe must be a probability in [0, 1], --kempe-max-chain an integer >= 0"
-                      << std::endl;
-            std::exit(1);
-        }
-        if (prob) c.kempe = v;
-        else c.kempe_max_chain = (int)v;
-        args.erase(it, it + 2);
-    }
-    if (auto it = std::find(args.begin(), args.end(), "--slot-swap"); it != args.end()) {
-        char* end = nullptr;
-        const double v = it + 1 == args.end() ? -1.0 : std::strtod((it + 1)->c_str(), &end);
-        if (!(v >= 0 && v == std::floor(v) && v <= INT_MAX) || !end || *end || (it + 1)->empty()) {
-            std::cerr << "Error: --slot-swap must be a non-negative integer" << std::endl;
-            std::exit(1);
-        }
-        c.slot_swap = (int)v;
-        args.erase(it, it + 2);
-    }
-    for (const char* k : {"--lahc", "--lahc-history"}) {
-        auto it = std::find(args.begin(), args.end(), k);
-        if (it == args.end()) continue;
-        const bool hist = std::string(k) == "--lahc-history";
-        char* end = nullptr;
-        const double v = it + 1 == args.end() ? -1.0 : std::strtod((it + 1)->c_str(), &end);
-        if (!(v >= (hist ? 1 : 0) && v == std::floor(v) && v <= INT_MAX) || !end || *end || (it + 1)->empty()) {
-            std::cerr << "Error: " << k << " must be " << (hist ? "a positive integer" : "a non-negative integer")
-                      << std::endl;
-            std::exit(1);
-        }
-        (hist ? c.lahc_history : c.lahc) = (int)v;
-        args.erase(it, it + 2);
-    }
-    if (auto it = std::find(args.begin(), args.end(), "--lahc-swap"); it != args.end()) {
-        char* end = nullptr;
-        const double v = it + 1 == args.end() ? -1.0 : std::strtod((it + 1)->c_str(), &end);
-        if (!(v >= 0.0 && v <= 1.0) || !end || *end || (it + 1)->empty()) {
-            std::cerr << "Error: --lahc-swap must be a probability in [0, 1]" << std::endl;
-            std::exit(1);
-        }
-        c.lahc_swap = v;
-        args.erase(it, it + 2);
-    }
-    if (auto it = std::find(args.begin(), args.end(), "--crossover-repair"); it != args.end()) {
-        c.cx_repair = true;
-        args.erase(it);
-    }
-    if (auto it = std::find(args.begin(), args.end(), "--crossover"); it != args.end()) {
-        if (it + 1 == args.end() || (*(it + 1) != "uniform" && *(it + 1) != "guided")) {
-            std::cerr << "Error: --crossover must be uniform or guided" << std::endl;
-            std::exit(1);
-        }
-        c.guided = *(it + 1) == "guided";
-        args.erase(it, it + 2);
-    }
-    if (c.cx_repair && !c.guided) {
-        std::cerr << "Error: --crossover-repair needs --crossover guided" << std::endl;
-        std::exit(1);
-    }
+    Stages& s = c.stage;
+    c.rccl = take_flag(args, "--rccl");
+    if (take_flag(args, "--stagger")) c.stagger = 2;
+    c.report = take_flag(args, "--report");
+    s.unique = take_flag(args, "--unique");
+    take_choice(args, "--init", "random", "greedy", "--init must be random or greedy", s.greedy);
+    // these two alone read an empty word as 0
+    const char* kempe_msg = "--kempe must be a probability in [0, 1], --kempe-max-chain an integer >= 0";
+    take_prob(args, "--kempe", kempe_msg, s.kempe, true);
+    take_int(args, "--kempe-max-chain", 0, kempe_msg, s.kempe_max_chain, true);
+    take_int(args, "--slot-swap", 0, "--slot-swap must be a non-negative integer", s.slot_swap);
+    take_int(args, "--lahc", 0, "--lahc must be a non-negative integer", s.lahc);
+    take_int(args, "--lahc-history", 1, "--lahc-history must be a positive integer", s.lahc_history);
+    take_prob(args, "--lahc-swap", "--lahc-swap must be a probability in [0, 1]", s.lahc_swap);
+    s.cx_repair = take_flag(args, "--crossover-repair");
+    take_choice(args, "--crossover", "uniform", "guided", "--crossover must be uniform or guided", s.guided);
+    if (s.cx_repair && !s.guided) bad_flag("--crossover-repair needs --crossover guided");
     for (const char* k : {"--gpus", "--islands", "--pop", "--generations", "--children", "--stagger-parts"}) {
         auto it = std::find(args.begin(), args.end(), k);
         if (it != args.end()) {
@@ -598,6 +586,50 @@ double seconds_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
+// A stage's per-row outputs, appended call after call on the device and read once at the
+// end, so that no generation waits for them: K int32 columns of `cap` rows (column k at
+// col(k)) and, where asked for, a uint8 column. A stage that is off never allocates its log.
+template <int K>
+struct RunLog {
+    struct Host { std::vector<int32_t> col[K]; std::vector<uint8_t> bytes; long rows = 0; };
+    int32_t* data = nullptr;
+    uint8_t* bytes = nullptr;
+    long cap = 0, used = 0;
+    const char* what = "";                            // of reserve()'s "more ... than planned for"
+
+    void alloc(long rows, const char* what_, bool with_bytes = false) {
+        cap = rows;
+        what = what_;
+        check_hip(hipMalloc(&data, 4 * (size_t)K * cap), "hipMalloc");
+        if (with_bytes) check_hip(hipMalloc(&bytes, (size_t)cap), "hipMalloc");
+    }
+    int32_t* col(int k) const { return data + k * cap; }
+    // room for the next n rows: their offset
+    long reserve(long n) {
+        if (used + n > cap) die(std::string("more ") + what + " than planned for");
+        used += n;
+        return used - n;
+    }
+    // the rows so far on the host, once the streams that wrote them have finished
+    Host fetch() const {
+        Host h;
+        h.rows = used;
+        for (int k = 0; k < K; k++) {
+            h.col[k].resize(used);
+            if (used) check_hip(hipMemcpy(h.col[k].data(), col(k), 4 * (size_t)used, hipMemcpyDeviceToHost), "hipMemcpy");
+        }
+        if (bytes) {
+            h.bytes.resize(used);
+            if (used) check_hip(hipMemcpy(h.bytes.data(), bytes, (size_t)used, hipMemcpyDeviceToHost), "hipMemcpy");
+        }
+        return h;
+    }
+    void release() {
+        if (data) (void)hipFree(data);
+        if (bytes) (void)hipFree(bytes);
+    }
+};
+
 struct Island {
     int id = 0, device = 0, N = 0, C = 0, E = 0, max_steps = 0;
     long seed = 0;
@@ -627,45 +659,35 @@ struct Island {
     hipStream_t op_stream = nullptr;                  // the stream that operation ran on
     std::vector<int> pending;                         // parts searched, not yet replaced (breed order)
     int last_replace = 0;
+    Stages stage;
     // --unique: every replacement is tt_ga_replace_unique; replacement number r leaves its
-    // kept count in kept_log[r] on the device (the initial sort, C = 0, has none), read once
-    // at the end, so no generation waits for it; children = those that went through a replacement
-    bool unique = false;
-    bool greedy = false;                              // --init greedy
+    // kept count in row r of kept_log (the initial sort, C = 0, has none); children = those
+    // that went through a replacement
     uint8_t* keep = nullptr;                          // [C], part j's flags at keep + off
-    int32_t* kept_log = nullptr;
-    long kept_cap = 0, kept_used = 0, children = 0;
-    // --kempe: tt_kempe_move on every sub-batch between its breed and its search; each
-    // call leaves its chain lengths in the next n entries of chain_log on the device,
-    // read once at the end, so no generation waits for them
-    double kempe = 0.0;
-    int kempe_max_chain = 0;
-    int32_t* chain_log = nullptr;
-    long chain_cap = 0, chain_used = 0;
-    // --slot-swap: tt_slot_swap behind every search; each call leaves its gains in the next
-    // n entries of swap_log and its passes in the n entries swap_cap further on, read once
-    // at the end, so no generation waits for them
-    int slot_swap = 0;
-    int32_t* swap_log = nullptr;
-    long swap_cap = 0, swap_used = 0;
-    // --lahc: tt_lahc behind every search (and timeslot swap); each call leaves its gains in
-    // the next n entries of lahc_log, its accepted counts lahc_cap further on and the rows'
-    // feasible flags in lahc_feas, read once at the end
-    int lahc = 0, lahc_history = 500;
-    double lahc_swap = 0.5;
-    int32_t* lahc_log = nullptr;
-    uint8_t* lahc_feas = nullptr;
-    long lahc_cap = 0, lahc_used = 0;
-    // --crossover guided: tt_ga_breed_guided breeds, in the event order cx_order; each call
-    // leaves its costs in the next n entries of cx_log, its repaired counts cx_cap further on
-    // and the children's flags in cx_flags, read once at the end
-    bool guided = false, cx_repair = false;
-    int32_t *cx_order = nullptr, *cx_log = nullptr;
-    uint8_t* cx_flags = nullptr;
-    long cx_cap = 0, cx_used = 0;
+    RunLog<1> kept_log;
+    long children = 0;
+    RunLog<1> chain_log;                              // --kempe: every child's chain length
+    RunLog<2> swap_log;                               // --slot-swap: every searched row's gain and passes
+    RunLog<2> lahc_log;                               // --lahc: every searched row's gain, accepted and feasible flag
+    RunLog<2> cx_log;                                 // --crossover guided: every child's cost, repaired and flags
+    int32_t* ev_order = nullptr;                      // event_order()'s, once computed
 
     size_t work_bytes(int n) const {
-        return std::max<size_t>(unique ? tt_ga_unique_work_bytes(N, n, E) : tt_ga_work_bytes(N, E), 16);
+        return std::max<size_t>(stage.unique ? tt_ga_unique_work_bytes(N, n, E) : tt_ga_work_bytes(N, E), 16);
+    }
+
+    // tt_greedy_order's event order (--init greedy, --crossover guided): computed on first
+    // use, finished on return, and kept for the island's life
+    const int32_t* event_order() {
+        if (!ev_order) {
+            void* scratch = nullptr;
+            check_hip(hipMalloc(&ev_order, 4 * (size_t)E), "hipMalloc");
+            check_hip(hipMalloc(&scratch, tt_greedy_work_bytes(tp)), "hipMalloc");
+            check_tt(tt_greedy_order(tp, ev_order, scratch, st), "tt_greedy_order");
+            check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
+            check_hip(hipFree(scratch), "hipFree");
+        }
+        return ev_order;
     }
 
     void setup(const Instance& inst, long replacements) {
@@ -685,35 +707,17 @@ struct Island {
         check_hip(hipMemcpy(rng_child, s.data() + N, 8 * (size_t)C, hipMemcpyHostToDevice), "hipMemcpy");
         check_hip(hipMalloc(&flags, (size_t)C), "hipMalloc");
         if (C >= kLptMinChildren) check_hip(hipMalloc(&order, 4 * (size_t)C), "hipMalloc");
-        if (unique) {
-            kept_cap = std::max(replacements, 1L);
+        const long bred = std::max(replacements / parts * C, 1L);      // generations x children
+        if (stage.unique) {
             check_hip(hipMalloc(&keep, (size_t)C), "hipMalloc");
-            check_hip(hipMalloc(&kept_log, 4 * (size_t)kept_cap), "hipMalloc");
-            check_hip(hipMemset(kept_log, 0, 4 * (size_t)kept_cap), "hipMemset");
+            kept_log.alloc(std::max(replacements, 1L), "replacements");
         }
-        if (kempe > 0) {
-            chain_cap = std::max(replacements / parts * C, 1L);        // generations x children
-            check_hip(hipMalloc(&chain_log, 4 * (size_t)chain_cap), "hipMalloc");
-        }
-        if (slot_swap > 0) {
-            swap_cap = N + std::max(replacements / parts * C, 1L);     // the members + generations x children
-            check_hip(hipMalloc(&swap_log, 2 * 4 * (size_t)swap_cap), "hipMalloc");
-        }
-        if (lahc > 0) {
-            lahc_cap = N + std::max(replacements / parts * C, 1L);     // the members + generations x children
-            check_hip(hipMalloc(&lahc_log, 2 * 4 * (size_t)lahc_cap), "hipMalloc");
-            check_hip(hipMalloc(&lahc_feas, (size_t)lahc_cap), "hipMalloc");
-        }
-        if (guided) {
-            cx_cap = std::max(replacements / parts * C, 1L);           // generations x children
-            check_hip(hipMalloc(&cx_log, 2 * 4 * (size_t)cx_cap), "hipMalloc");
-            check_hip(hipMalloc(&cx_flags, (size_t)cx_cap), "hipMalloc");
-            void* ev_work = nullptr;                                   // the order's scratch, needed once
-            check_hip(hipMalloc(&cx_order, 4 * (size_t)E), "hipMalloc");
-            check_hip(hipMalloc(&ev_work, tt_greedy_work_bytes(tp)), "hipMalloc");
-            check_tt(tt_greedy_order(tp, cx_order, ev_work, st), "tt_greedy_order");
-            check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
-            check_hip(hipFree(ev_work), "hipFree");
+        if (stage.kempe > 0) chain_log.alloc(bred, "Kempe moves");
+        if (stage.slot_swap > 0) swap_log.alloc(N + bred, "timeslot-swap rows");          // the members too
+        if (stage.lahc > 0) lahc_log.alloc(N + bred, "late-acceptance rows", true);       // the members too
+        if (stage.guided) {
+            cx_log.alloc(bred, "guided crossovers", true);
+            event_order();                            // before any part's stream breeds in it
         }
         migrant_bytes = 2 * (size_t)E + 13;
         check_hip(hipMalloc(&send_best, migrant_bytes), "hipMalloc");
@@ -751,26 +755,16 @@ struct Island {
 
     // ga.cpp:429-434 for every member, then the population is sorted
     void initialize() {
-        if (greedy) {
-            // the event order and its scratch are needed once: freed when the stream has used them
-            int32_t* ev_order = nullptr;
-            void* ev_work = nullptr;
-            check_hip(hipMalloc(&ev_order, 4 * (size_t)E), "hipMalloc");
-            check_hip(hipMalloc(&ev_work, tt_greedy_work_bytes(tp)), "hipMalloc");
-            check_tt(tt_greedy_order(tp, ev_order, ev_work, st), "tt_greedy_order");
-            check_tt(tt_greedy_init(tp, ev_order, rng_init, pop.slot, pop.room, N, st), "tt_greedy_init");
-            check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
-            check_hip(hipFree(ev_order), "hipFree");
-            check_hip(hipFree(ev_work), "hipFree");
-        } else {
+        if (stage.greedy)
+            check_tt(tt_greedy_init(tp, event_order(), rng_init, pop.slot, pop.room, N, st), "tt_greedy_init");
+        else
             check_tt(tt_random_init(tp, rng_init, pop.slot, pop.room, N, st), "tt_random_init");
-        }
         check_tt(tt_local_search_eval(tp, pop.slot, pop.room, rng_init, N, max_steps, p1, p2, p3, nullptr, pop.hcv,
                                       pop.scv, pop.feasible, pop.penalty, st),
                  "tt_local_search_eval");
-        if (slot_swap > 0) swap_slots(pop, st);
-        if (lahc > 0) late_acceptance(pop, rng_init, st);
-        if (unique)
+        if (stage.slot_swap > 0) swap_slots(pop, st);
+        if (stage.lahc > 0) late_acceptance(pop, rng_init, st);
+        if (stage.unique)
             check_tt(tt_ga_replace_unique(tp, pop.slot, pop.room, pop.hcv, pop.scv, pop.feasible, pop.penalty, N,
                                           pop.slot, pop.room, pop.hcv, pop.scv, pop.feasible, pop.penalty, 0, nullptr,
                                           nullptr, 0, work, st),
@@ -792,18 +786,30 @@ struct Island {
         return v;
     }
 
+    // every part's stream (part 0's is st) has finished: the logs can be read
+    void finish() {
+        for (const Part& p : part) check_hip(hipStreamSynchronize(p.s), "hipStreamSynchronize");
+    }
+
+    // a log's rows with every sub-batch replaced
+    template <int K>
+    typename RunLog<K>::Host read(const RunLog<K>& log) {
+        flush();
+        finish();
+        return log.fetch();
+    }
+
     // breed n children into rows [off, off + n) on stream s
     void breed(int off, int n, hipStream_t s) {
         Pop c = child_rows(off, n);
-        if (guided) {
-            if (cx_used + n > cx_cap) die("more guided crossovers than planned for");
-            check_tt(tt_ga_breed_guided(tp, pop.slot, pop.room, pop.penalty, N, cx_order, rng_child + off, n, p_cross,
-                                        p_mut, 1, cx_repair, c.slot, c.room, flags + off, cx_log + cx_used,
-                                        cx_log + cx_cap + cx_used, s),
+        if (stage.guided) {
+            const long at = cx_log.reserve(n);
+            check_tt(tt_ga_breed_guided(tp, pop.slot, pop.room, pop.penalty, N, event_order(), rng_child + off, n,
+                                        p_cross, p_mut, 1, stage.cx_repair, c.slot, c.room, flags + off,
+                                        cx_log.col(0) + at, cx_log.col(1) + at, s),
                      "tt_ga_breed_guided");
-            check_hip(hipMemcpyAsync(cx_flags + cx_used, flags + off, (size_t)n, hipMemcpyDeviceToDevice, s),
+            check_hip(hipMemcpyAsync(cx_log.bytes + at, flags + off, (size_t)n, hipMemcpyDeviceToDevice, s),
                       "hipMemcpyAsync");
-            cx_used += n;
             return;
         }
         check_tt(tt_ga_breed(tp, pop.slot, pop.room, pop.penalty, N, rng_child + off, n, p_cross, p_mut, 1, c.slot,
@@ -813,26 +819,17 @@ struct Island {
 
     // the --crossover guided line (ttga/ga.py crossover_line)
     Json crossover_report() {
-        flush();
-        std::vector<int32_t> cost(cx_used), rep(cx_used);
-        std::vector<uint8_t> fl(cx_used);
-        for (const Part& p : part) check_hip(hipStreamSynchronize(p.s), "hipStreamSynchronize");
-        check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
-        if (cx_used) {
-            check_hip(hipMemcpy(cost.data(), cx_log, 4 * cost.size(), hipMemcpyDeviceToHost), "hipMemcpy");
-            check_hip(hipMemcpy(rep.data(), cx_log + cx_cap, 4 * rep.size(), hipMemcpyDeviceToHost), "hipMemcpy");
-            check_hip(hipMemcpy(fl.data(), cx_flags, fl.size(), hipMemcpyDeviceToHost), "hipMemcpy");
-        }
+        const auto h = read(cx_log);
         long crossed = 0, clean = 0, total = 0, repaired = 0;
-        for (long i = 0; i < cx_used; i++) {
-            const bool x = (fl[i] & 1) != 0;
+        for (long i = 0; i < h.rows; i++) {
+            const bool x = (h.bytes[i] & 1) != 0;
             crossed += x;
-            clean += x && cost[i] == 0;
-            total += cost[i];
-            repaired += rep[i];
+            clean += x && h.col[0][i] == 0;
+            total += h.col[0][i];
+            repaired += h.col[1][i];
         }
         Json k;
-        k.obj["children"] = Json::I(cx_used);
+        k.obj["children"] = Json::I(h.rows);
         k.obj["crossed"] = Json::I(crossed);
         k.obj["clean"] = Json::I(clean);
         k.obj["meanCost"] = Json::D(crossed ? (double)total / (double)crossed : 0.0);
@@ -843,28 +840,22 @@ struct Island {
     // --kempe: the Kempe-chain move on rows [off, off + n) on s, from the children's own streams
     void kempe_move(int off, int n, hipStream_t s) {
         Pop c = child_rows(off, n);
-        if (chain_used + n > chain_cap) die("more Kempe moves than planned for");
-        check_tt(tt_kempe_move(tp, c.slot, c.room, rng_child + off, n, kempe, kempe_max_chain, chain_log + chain_used,
-                               s),
+        check_tt(tt_kempe_move(tp, c.slot, c.room, rng_child + off, n, stage.kempe, stage.kempe_max_chain,
+                               chain_log.col(0) + chain_log.reserve(n), s),
                  "tt_kempe_move");
-        chain_used += n;
     }
 
-    // the --kempe line: every call's chain lengths in one copy (ttga/ga.py kempe_line)
+    // the --kempe line (ttga/ga.py kempe_line)
     Json kempe_report() {
-        flush();
-        std::vector<int32_t> len(chain_used);
-        for (const Part& p : part) check_hip(hipStreamSynchronize(p.s), "hipStreamSynchronize");
-        if (!len.empty())
-            check_hip(hipMemcpy(len.data(), chain_log, 4 * len.size(), hipMemcpyDeviceToHost), "hipMemcpy");
+        const auto h = read(chain_log);
         long moved = 0, rejected = 0, events = 0;
-        for (int32_t v : len) {
+        for (int32_t v : h.col[0]) {
             moved += v > 0;
             rejected += v < 0;
             if (v > 0) events += v;
         }
         Json k;
-        k.obj["children"] = Json::I(chain_used);
+        k.obj["children"] = Json::I(h.rows);
         k.obj["moved"] = Json::I(moved);
         k.obj["rejected"] = Json::I(rejected);
         k.obj["meanChain"] = Json::D(moved ? (double)events / (double)moved : 0.0);
@@ -874,31 +865,23 @@ struct Island {
     // --slot-swap: the timeslot-swap descent on the searched rows r on s, behind their search
     // and evaluation; their scv and penalty are lowered in place
     void swap_slots(const Pop& r, hipStream_t s) {
-        if (swap_used + r.n > swap_cap) die("more timeslot-swap rows than planned for");
-        check_tt(tt_slot_swap(tp, r.slot, r.n, slot_swap, r.scv, r.penalty, swap_log + swap_used,
-                              swap_log + swap_cap + swap_used, nullptr, s),
+        const long at = swap_log.reserve(r.n);
+        check_tt(tt_slot_swap(tp, r.slot, r.n, stage.slot_swap, r.scv, r.penalty, swap_log.col(0) + at,
+                              swap_log.col(1) + at, nullptr, s),
                  "tt_slot_swap");
-        swap_used += r.n;
     }
 
-    // the --slot-swap line: every call's gains and passes in two copies (ttga/ga.py slot_swap_line)
+    // the --slot-swap line (ttga/ga.py slot_swap_line)
     Json slot_swap_report() {
-        flush();
-        std::vector<int32_t> gain(swap_used), pass(swap_used);
-        for (const Part& p : part) check_hip(hipStreamSynchronize(p.s), "hipStreamSynchronize");
-        check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
-        if (swap_used) {
-            check_hip(hipMemcpy(gain.data(), swap_log, 4 * gain.size(), hipMemcpyDeviceToHost), "hipMemcpy");
-            check_hip(hipMemcpy(pass.data(), swap_log + swap_cap, 4 * pass.size(), hipMemcpyDeviceToHost), "hipMemcpy");
-        }
+        const auto h = read(swap_log);
         long improved = 0, passes = 0, total = 0;
-        for (long i = 0; i < swap_used; i++) {
-            improved += pass[i] > 0;
-            passes += pass[i];
-            total += gain[i];
+        for (long i = 0; i < h.rows; i++) {
+            improved += h.col[1][i] > 0;
+            passes += h.col[1][i];
+            total += h.col[0][i];
         }
         Json k;
-        k.obj["rows"] = Json::I(swap_used);
+        k.obj["rows"] = Json::I(h.rows);
         k.obj["improved"] = Json::I(improved);
         k.obj["gain"] = Json::I(total);
         k.obj["meanPasses"] = Json::D(improved ? (double)passes / (double)improved : 0.0);
@@ -908,36 +891,26 @@ struct Island {
     // --lahc: the late-acceptance walk of the searched rows r (streams g) on s, behind their
     // search, evaluation and timeslot swap; their scv and penalty are lowered in place
     void late_acceptance(const Pop& r, int64_t* g, hipStream_t s) {
-        if (lahc_used + r.n > lahc_cap) die("more late-acceptance rows than planned for");
-        check_tt(tt_lahc(tp, r.slot, r.room, g, r.n, lahc, lahc_history, lahc_swap, r.scv, r.penalty,
-                         lahc_log + lahc_used, lahc_log + lahc_cap + lahc_used, nullptr, s),
+        const long at = lahc_log.reserve(r.n);
+        check_tt(tt_lahc(tp, r.slot, r.room, g, r.n, stage.lahc, stage.lahc_history, stage.lahc_swap, r.scv, r.penalty,
+                         lahc_log.col(0) + at, lahc_log.col(1) + at, nullptr, s),
                  "tt_lahc");
-        check_hip(hipMemcpyAsync(lahc_feas + lahc_used, r.feasible, (size_t)r.n, hipMemcpyDeviceToDevice, s),
+        check_hip(hipMemcpyAsync(lahc_log.bytes + at, r.feasible, (size_t)r.n, hipMemcpyDeviceToDevice, s),
                   "hipMemcpyAsync");
-        lahc_used += r.n;
     }
 
     // the --lahc line (ttga/ga.py lahc_line)
     Json lahc_report() {
-        flush();
-        std::vector<int32_t> gain(lahc_used), acc(lahc_used);
-        std::vector<uint8_t> feas(lahc_used);
-        for (const Part& p : part) check_hip(hipStreamSynchronize(p.s), "hipStreamSynchronize");
-        check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
-        if (lahc_used) {
-            check_hip(hipMemcpy(gain.data(), lahc_log, 4 * gain.size(), hipMemcpyDeviceToHost), "hipMemcpy");
-            check_hip(hipMemcpy(acc.data(), lahc_log + lahc_cap, 4 * acc.size(), hipMemcpyDeviceToHost), "hipMemcpy");
-            check_hip(hipMemcpy(feas.data(), lahc_feas, feas.size(), hipMemcpyDeviceToHost), "hipMemcpy");
-        }
+        const auto h = read(lahc_log);
         long searched = 0, improved = 0, accepted = 0, total = 0;
-        for (long i = 0; i < lahc_used; i++) {
-            searched += feas[i] != 0;
-            improved += gain[i] > 0;
-            accepted += acc[i];
-            total += gain[i];
+        for (long i = 0; i < h.rows; i++) {
+            searched += h.bytes[i] != 0;
+            improved += h.col[0][i] > 0;
+            accepted += h.col[1][i];
+            total += h.col[0][i];
         }
         Json k;
-        k.obj["rows"] = Json::I(lahc_used);
+        k.obj["rows"] = Json::I(h.rows);
         k.obj["searched"] = Json::I(searched);
         k.obj["improved"] = Json::I(improved);
         k.obj["accepted"] = Json::I(accepted);
@@ -964,11 +937,10 @@ struct Island {
 
     void replace(int off, int n, hipStream_t s, void* w) {
         Pop c = child_rows(off, n);
-        if (unique) {
-            if (kept_used >= kept_cap) die("more replacements than planned for");
+        if (stage.unique) {
             check_tt(tt_ga_replace_unique(tp, pop.slot, pop.room, pop.hcv, pop.scv, pop.feasible, pop.penalty, N, c.slot,
                                           c.room, c.hcv, c.scv, c.feasible, c.penalty, n, keep + off,
-                                          kept_log + kept_used++, 0, w, s),
+                                          kept_log.col(0) + kept_log.reserve(1), 0, w, s),
                      "tt_ga_replace_unique");
             children += n;
             return;
@@ -979,23 +951,21 @@ struct Island {
     }
 
     // the --unique line of the population with every sub-batch replaced: the kept counts
-    // of all replacements in one copy, and the first occurrences of the genomes
+    // of all replacements, and the first occurrences of the genomes
     Json unique_report(int proc, int island) {
-        flush();
-        std::vector<int32_t> kept(kept_used), first(N);
+        const auto kept = read(kept_log);
+        std::vector<int32_t> first(N);
         int32_t* d_first = nullptr;
         void* d_work = nullptr;
         check_hip(hipMalloc(&d_first, 4 * (size_t)N), "hipMalloc");
         check_hip(hipMalloc(&d_work, std::max<size_t>(tt_genome_work_bytes(N, E), 16)), "hipMalloc");
         check_tt(tt_genome_first(tp, pop.slot, pop.room, N, d_first, 0, d_work, st), "tt_genome_first");
         check_hip(hipMemcpyAsync(first.data(), d_first, 4 * (size_t)N, hipMemcpyDeviceToHost, st), "hipMemcpy");
-        if (!kept.empty())
-            check_hip(hipMemcpyAsync(kept.data(), kept_log, 4 * kept.size(), hipMemcpyDeviceToHost, st), "hipMemcpy");
         check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
         (void)hipFree(d_first);
         (void)hipFree(d_work);
         long kept_sum = 0, distinct = 0;
-        for (size_t r = 0; r < kept.size(); r++) kept_sum += kept[r];
+        for (int32_t v : kept.col[0]) kept_sum += v;
         for (int i = 0; i < N; i++) distinct += first[i] == i;
         return unique_line(children, children - kept_sum, distinct, proc, island);
     }
@@ -1014,10 +984,10 @@ struct Island {
         breed(p.off, p.n, p.s);
         wrote_population(p.s);
         if (!pending.empty() && (int)pending.size() >= parts - 1) replace_oldest();   // replace(h - parts + 1) after breed(h)
-        if (kempe > 0) kempe_move(p.off, p.n, p.s);
+        if (stage.kempe > 0) kempe_move(p.off, p.n, p.s);
         search(p.off, p.n, p.s, p.work);
-        if (slot_swap > 0) swap_slots(child_rows(p.off, p.n), p.s);
-        if (lahc > 0) late_acceptance(child_rows(p.off, p.n), rng_child + p.off, p.s);
+        if (stage.slot_swap > 0) swap_slots(child_rows(p.off, p.n), p.s);
+        if (stage.lahc > 0) late_acceptance(child_rows(p.off, p.n), rng_child + p.off, p.s);
         pending.push_back(j);
         if ((int)pending.size() >= parts) replace_oldest();
     }
@@ -1071,7 +1041,7 @@ struct Island {
                   "hipMemcpy");
         check_hip(hipStreamSynchronize(p.s), "hipStreamSynchronize");
         // the child's source word: N - n + c from tt_ga_replace, N + c from tt_ga_replace_unique
-        const long k = unique ? N : N - p.n, end = unique ? N + p.n : N;
+        const long k = stage.unique ? N : N - p.n, end = stage.unique ? N + p.n : N;
         return src >= k && src < end ? (int)(p.off + src - k) : 0;
     }
 
@@ -1130,10 +1100,13 @@ struct Island {
         pop.release();
         child.release();
         for (void* p : {(void*)rng_init, (void*)rng_child, (void*)flags, (void*)order, (void*)send_best,
-                        (void*)send_second, (void*)recv_buf, (void*)keep, (void*)kept_log, (void*)chain_log,
-                        (void*)swap_log, (void*)lahc_log, (void*)lahc_feas, (void*)cx_order, (void*)cx_log,
-                        (void*)cx_flags})
+                        (void*)send_second, (void*)recv_buf, (void*)keep, (void*)ev_order})
             if (p) (void)hipFree(p);
+        kept_log.release();
+        chain_log.release();
+        swap_log.release();
+        lahc_log.release();
+        cx_log.release();
         for (size_t j = 0; j < part.size(); j++) {
             if (part[j].work) (void)hipFree(part[j].work);
             if (j > 0 && part[j].s) (void)hipStreamDestroy(part[j].s);
@@ -1190,16 +1163,7 @@ int main(int argc, char** argv) {
         I.seed = island_seed(ctl.seed, k);
         I.p1 = ctl.p1; I.p2 = ctl.p2; I.p3 = ctl.p3;
         I.parts = ctl.stagger >= 2 ? std::min(ctl.stagger, C) : 1;
-        I.unique = ctl.unique;
-        I.greedy = ctl.greedy;
-        I.kempe = ctl.kempe;
-        I.kempe_max_chain = ctl.kempe_max_chain;
-        I.slot_swap = ctl.slot_swap;
-        I.lahc = ctl.lahc;
-        I.lahc_history = ctl.lahc_history;
-        I.lahc_swap = ctl.lahc_swap;
-        I.guided = ctl.guided;
-        I.cx_repair = ctl.cx_repair;
+        I.stage = ctl.stage;
     }
     std::vector<ncclComm_t> comms(K, nullptr);
     if (rccl) {
@@ -1320,29 +1284,20 @@ int main(int argc, char** argv) {
         check_hip(hipMemcpy(sl.data(), I.pop.slot, I.E, hipMemcpyDeviceToHost), "hipMemcpy");
         check_hip(hipMemcpy(rm.data(), I.pop.room, I.E, hipMemcpyDeviceToHost), "hipMemcpy");
         out.line(solution_line(b.feasible, b.scv, b.hcv, sl, rm, k, seconds_since(t_begin)));
-        if (ctl.guided) out.line(I.crossover_report());
-        if (ctl.kempe > 0) out.line(I.kempe_report());
+        if (ctl.stage.guided) out.line(I.crossover_report());
+        if (ctl.stage.kempe > 0) out.line(I.kempe_report());
     }
-    if (ctl.unique)
-        for (int k = 0; k < K; k++) {
+    // then, kind by kind, the lines that every island prints
+    auto each_island = [&](bool on, auto line) {
+        for (int k = 0; on && k < K; k++) {
             check_hip(hipSetDevice(isl[k].device), "hipSetDevice");
-            out.line(isl[k].unique_report(k, k));
+            out.line(line(isl[k], k));
         }
-    if (ctl.slot_swap > 0)
-        for (int k = 0; k < K; k++) {
-            check_hip(hipSetDevice(isl[k].device), "hipSetDevice");
-            out.line(isl[k].slot_swap_report());
-        }
-    if (ctl.lahc > 0)
-        for (int k = 0; k < K; k++) {
-            check_hip(hipSetDevice(isl[k].device), "hipSetDevice");
-            out.line(isl[k].lahc_report());
-        }
-    if (ctl.report)
-        for (int k = 0; k < K; k++) {
-            check_hip(hipSetDevice(isl[k].device), "hipSetDevice");
-            out.line(isl[k].report(k, k));
-        }
+    };
+    each_island(ctl.stage.unique, [](Island& I, int k) { return I.unique_report(k, k); });
+    each_island(ctl.stage.slot_swap > 0, [](Island& I, int) { return I.slot_swap_report(); });
+    each_island(ctl.stage.lahc > 0, [](Island& I, int) { return I.lahc_report(); });
+    each_island(ctl.report, [](Island& I, int k) { return I.report(k, k); });
     out.line(run_final_line(K, C, seconds_since(t_start)));
     for (int k = 0; k < K; k++) {
         (void)hipSetDevice(isl[k].device);

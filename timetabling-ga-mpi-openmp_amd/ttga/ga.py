@@ -43,6 +43,8 @@ import types
 
 import numpy as np
 
+from .stages import validate
+
 # ga.cpp:389-397: -p 1 -> 200, -p 2 -> 1000, otherwise 2000
 MAX_STEPS = {1: 200, 2: 1000}
 
@@ -171,6 +173,37 @@ def _side_streams(dev, base, n: int) -> list:
     return pool[:n]
 
 
+# The stages whose per-row outputs are tallied on the device: what turns the stage on (for
+# {stage}_stats()'s error), the name of its row count, its int32 per-row outputs, the names
+# of its sums, and whether it also runs on the members in initialize()
+_TALLIED = {
+    "kempe": ("kempe > 0", "children", ("chain",), ("moved", "rejected", "chain_events"), False),
+    "slot_swap": ("slot_swap > 0", "rows", ("gain", "passes"), ("improved", "passes", "gain"), True),
+    "lahc": ("lahc > 0", "rows", ("gain", "accepted", "best_step"), ("searched", "improved", "accepted", "gain"), True),
+    "cx": ("crossover='guided'", "children", ("cost", "repaired"), ("crossed", "clean", "cost", "repaired"), False),
+}
+
+
+class Tally:
+    """A stage's device-side tally for calls on n rows: its int32 per-row
+    outputs `out[name]`, the int64 running `sums` (one entry per name), added
+    up on the stream behind each call, and on the host the `rows` it was called
+    on. The tensors join `register` (Island's record_stream pass)."""
+
+    def __init__(self, n: int, outputs, sums, dev, register: list):
+        import torch
+        self.out = {k: torch.zeros(n, dtype=torch.int32, device=dev) for k in outputs}
+        self.sums = torch.zeros(len(sums), dtype=torch.int64, device=dev)
+        self.rows = 0
+        register += [*self.out.values(), self.sums]
+
+    def add(self, rows: int, *scalars) -> None:
+        """The device scalars of one call on `rows` rows, in the sums' order."""
+        import torch
+        self.sums += torch.stack(scalars)
+        self.rows += rows
+
+
 class Island(Members):
     """One island: population [N] + C child slots, all device-resident.
 
@@ -240,6 +273,9 @@ class Island(Members):
     crossover_repair an event that clashes in both parents' slots goes to a
     slot of least cost. Everything else is unchanged. crossover="uniform"
     issues no new call at all. cx_stats() reports what the crossovers did.
+
+    `on` is the set of these stages that are on: "unique", "kempe",
+    "slot_swap", "lahc", "cx" (the {stage}_stats() that do not raise).
     """
 
     def __init__(self, dp, pop_size: int = 10, children: int = 1, max_steps: int = 200, seed: int = 1,
@@ -255,25 +291,8 @@ class Island(Members):
         leaves idle; every host read of the island (member, member_meta, best_thread)
         synchronises its stream first, and a caller that moves data between islands
         (migration) synchronises the device around it."""
+        validate(init, kempe, kempe_max_chain, slot_swap, lahc, lahc_history, lahc_swap, crossover, crossover_repair)
         import torch
-        if crossover not in ("uniform", "guided"):
-            raise ValueError("crossover must be 'uniform' or 'guided'")
-        if crossover_repair and crossover != "guided":
-            raise ValueError("crossover_repair needs crossover='guided'")
-        if init not in ("random", "greedy"):
-            raise ValueError("init must be 'random' or 'greedy'")
-        if not (0.0 <= float(kempe) <= 1.0):
-            raise ValueError("kempe must be a probability in [0, 1]")
-        if int(kempe_max_chain) < 0:
-            raise ValueError("kempe_max_chain must be >= 0 (0: no cap)")
-        if int(slot_swap) < 0:
-            raise ValueError("slot_swap must be >= 0 (0: off)")
-        if int(lahc) < 0:
-            raise ValueError("lahc must be >= 0 (0: off)")
-        if int(lahc_history) < 1:
-            raise ValueError("lahc_history must be >= 1")
-        if not (0.0 <= float(lahc_swap) <= 1.0):
-            raise ValueError("lahc_swap must be a probability in [0, 1]")
         if not (1 <= children <= pop_size):
             raise ValueError("need 1 <= children <= pop_size")
         if schedule not in ("batch", "staggered"):
@@ -321,7 +340,7 @@ class Island(Members):
             self._parts.append(types.SimpleNamespace(
                 off=r.start, n=n, child={k: v[r] for k, v in self.child.items()}, rng=self.rng_child[r],
                 flags=self.flags[r], work=dp.ga_unique_work(self.N, n) if self.unique else dp.ga_work(self.N),
-                stream=st))
+                stream=st, tally={}))
         self.work = self._parts[0].work
         # unique: each part's keep flags and kept count, the children dropped so far (added up
         # on the replacing stream) and, on the host, the children that went through a replacement
@@ -334,52 +353,18 @@ class Island(Members):
             self._init_kept = torch.zeros(1, dtype=torch.int32, device=dev)
             self._dropped = torch.zeros(1, dtype=torch.int64, device=dev)
             self._extra += [self._init_kept, self._dropped]
-        # kempe: each part's chain lengths and its running (moved, rejected, events moved),
-        # added up on the part's stream behind the move; the children moved on, on the host
-        if self.kempe > 0:
-            for p in self._parts:
-                p.chain = torch.zeros(p.n, dtype=torch.int32, device=dev)
-                p.kempe_sums = torch.zeros(3, dtype=torch.int64, device=dev)
-                self._extra += [p.chain, p.kempe_sums]
-        self._kempe_children = 0
-        # slot_swap: each part's (and the members') gains and passes and the running (rows
-        # improved, passes, gain), added up on the stream behind the call; the rows, on the host
-        if self.slot_swap > 0:
-            self._swap_init = types.SimpleNamespace(
-                gain=torch.zeros(self.N, dtype=torch.int32, device=dev),
-                passes=torch.zeros(self.N, dtype=torch.int32, device=dev),
-                sums=torch.zeros(3, dtype=torch.int64, device=dev))
-            self._extra += list(vars(self._swap_init).values())
-            for p in self._parts:
-                p.swap = types.SimpleNamespace(gain=torch.zeros(p.n, dtype=torch.int32, device=dev),
-                                               passes=torch.zeros(p.n, dtype=torch.int32, device=dev),
-                                               sums=torch.zeros(3, dtype=torch.int64, device=dev))
-                self._extra += list(vars(p.swap).values())
-        self._swap_rows = 0
-        # lahc: each part's (and the members') gain, accepted and best_step and the running
-        # (rows searched, rows improved, accepted, gain), added up on the stream behind the
-        # call; the rows, on the host
-        if self.lahc > 0:
-            def lahc_buffers(n):
-                b = types.SimpleNamespace(gain=torch.zeros(n, dtype=torch.int32, device=dev),
-                                          accepted=torch.zeros(n, dtype=torch.int32, device=dev),
-                                          best_step=torch.zeros(n, dtype=torch.int32, device=dev),
-                                          sums=torch.zeros(4, dtype=torch.int64, device=dev))
-                self._extra += list(vars(b).values())
-                return b
-            self._lahc_init = lahc_buffers(self.N)
-            for p in self._parts:
-                p.lahc = lahc_buffers(p.n)
-        self._lahc_rows = 0
-        # guided crossover: each part's cost and repaired and the running (crossed, clean, cost,
-        # repaired), added up on the part's stream behind the breed; the children, on the host
-        if self.crossover == "guided":
-            for p in self._parts:
-                p.cx = types.SimpleNamespace(cost=torch.zeros(p.n, dtype=torch.int32, device=dev),
-                                             repaired=torch.zeros(p.n, dtype=torch.int32, device=dev),
-                                             sums=torch.zeros(4, dtype=torch.int64, device=dev))
-                self._extra += list(vars(p.cx).values())
-        self._cx_children = 0
+        # the stages that are on, and their tallies: one per part, and the members' where the
+        # stage also runs in initialize()
+        self.on = {stage for stage, on in (("unique", self.unique), ("kempe", self.kempe > 0),
+                                           ("slot_swap", self.slot_swap > 0), ("lahc", self.lahc > 0),
+                                           ("cx", self.crossover == "guided")) if on}
+        self._init_tally = {}
+        for stage, (_, _, outputs, sums, in_init) in _TALLIED.items():
+            if stage in self.on:
+                if in_init:
+                    self._init_tally[stage] = Tally(self.N, outputs, sums, dev, self._extra)
+                for p in self._parts:
+                    p.tally[stage] = Tally(p.n, outputs, sums, dev, self._extra)
         self._replaced = 0
         self._pending = []                            # parts searched but not yet replaced, in breed order
         self._last_replace = 0                        # part whose work buffer holds the last replace's source
@@ -498,9 +483,9 @@ class Island(Members):
             self.dp.local_search(p["slot"], p["room"], self.rng_init, self.max_steps, self.p1, self.p2, self.p3,
                                  out=(p["hcv"], p["scv"], p["feasible"], p["penalty"]))
             if self.slot_swap > 0:
-                self._slot_swap(p, self._swap_init)
+                self._slot_swap(p, self._init_tally["slot_swap"])
             if self.lahc > 0:
-                self._lahc(p, self.rng_init, self._lahc_init)
+                self._lahc(p, self.rng_init, self._init_tally["lahc"])
             if self.unique:
                 self.dp.ga_replace_unique(p, None, self.work, n_kept=self._init_kept)
             else:
@@ -549,9 +534,9 @@ class Island(Members):
                 self._kempe(p)
             self._search(p.child, p.rng, p.work)
             if self.slot_swap > 0:
-                self._slot_swap(p.child, p.swap)
+                self._slot_swap(p.child, p.tally["slot_swap"])
             if self.lahc > 0:
-                self._lahc(p.child, p.rng, p.lahc)
+                self._lahc(p.child, p.rng, p.tally["lahc"])
             self._pending.append(j)
             if len(self._pending) >= self.parts:
                 self._replace_oldest()
@@ -559,94 +544,75 @@ class Island(Members):
     def _breed_guided(self, p):
         """tt_ga_breed_guided for part p (on its stream, the current one) and
         its counts, summed on the device behind the breed."""
-        import torch
-        b = p.cx
+        t = p.tally["cx"]
+        cost, repaired = t.out["cost"], t.out["repaired"]
         self.dp.ga_breed_guided(self.pop["slot"], self.pop["room"], self.pop["penalty"], p.rng, p.child["slot"],
                                 p.child["room"], p.flags, self.p_cross, self.p_mut, self.skip,
-                                repair=self.crossover_repair, cost=b.cost, repaired=b.repaired)
+                                repair=self.crossover_repair, cost=cost, repaired=repaired)
         crossed = (p.flags & 1) != 0
-        b.sums += torch.stack([crossed.sum(), (crossed & (b.cost == 0)).sum(), b.cost.sum(), b.repaired.sum()])
-        self._cx_children += p.n
-
-    def cx_stats(self) -> dict:
-        """Island(crossover="guided"): the children bred, how many of them
-        crossed, how many of those came out with cost 0, and the cost and the
-        repaired events summed over the crossed children, as Python ints.
-        Pending sub-batches are replaced first; synchronises."""
-        if self.crossover != "guided":
-            raise ValueError("cx_stats() needs Island(crossover='guided')")
-        self.flush()
-        self.sync()
-        crossed, clean, cost, repaired = (int(v) for v in sum(p.cx.sums.cpu() for p in self._parts).tolist())
-        return {"children": int(self._cx_children), "crossed": crossed, "clean": clean, "cost": cost,
-                "repaired": repaired}
+        t.add(p.n, crossed.sum(), (crossed & (cost == 0)).sum(), cost.sum(), repaired.sum())
 
     def _kempe(self, p):
         """tt_kempe_move on the children of part p (on its stream, the current
         one) and its counts, summed on the device behind the move."""
-        import torch
-        self.dp.kempe_move(p.child["slot"], p.child["room"], p.rng, self.kempe, self.kempe_max_chain, p.chain)
-        p.kempe_sums += torch.stack([(p.chain > 0).sum(), (p.chain < 0).sum(), p.chain.clamp(min=0).sum()])
-        self._kempe_children += p.n
+        t = p.tally["kempe"]
+        chain = t.out["chain"]
+        self.dp.kempe_move(p.child["slot"], p.child["room"], p.rng, self.kempe, self.kempe_max_chain, chain)
+        t.add(p.n, (chain > 0).sum(), (chain < 0).sum(), chain.clamp(min=0).sum())
 
-    def _slot_swap(self, rows, b):
+    def _slot_swap(self, rows, t):
         """tt_slot_swap on the searched rows (on the current stream, behind
         their search and evaluation) and its counts, summed on the device
         behind the call."""
-        import torch
-        self.dp.slot_swap(rows["slot"], self.slot_swap, scv=rows["scv"], penalty=rows["penalty"], gain=b.gain,
-                          passes=b.passes)
-        b.sums += torch.stack([(b.passes > 0).sum(), b.passes.sum(), b.gain.sum()])
-        self._swap_rows += int(rows["slot"].shape[0])
+        gain, passes = t.out["gain"], t.out["passes"]
+        self.dp.slot_swap(rows["slot"], self.slot_swap, scv=rows["scv"], penalty=rows["penalty"], gain=gain,
+                          passes=passes)
+        t.add(int(rows["slot"].shape[0]), (passes > 0).sum(), passes.sum(), gain.sum())
 
-    def _lahc(self, rows, rng, b):
+    def _lahc(self, rows, rng, t):
         """tt_lahc on the searched rows (on the current stream, behind their
         search and evaluation) and its counts, summed on the device behind the
         call. The rows that walk are the feasible ones: the call's own gate is
         tt_eval's hcv."""
-        import torch
+        gain, accepted = t.out["gain"], t.out["accepted"]
         self.dp.lahc(rows["slot"], rows["room"], rng, self.lahc, self.lahc_history, self.lahc_swap, scv=rows["scv"],
-                     penalty=rows["penalty"], gain=b.gain, accepted=b.accepted, best_step=b.best_step)
-        b.sums += torch.stack([(rows["feasible"] != 0).sum(), (b.gain > 0).sum(), b.accepted.sum(), b.gain.sum()])
-        self._lahc_rows += int(rows["slot"].shape[0])
+                     penalty=rows["penalty"], gain=gain, accepted=accepted, best_step=t.out["best_step"])
+        t.add(int(rows["slot"].shape[0]), (rows["feasible"] != 0).sum(), (gain > 0).sum(), accepted.sum(), gain.sum())
+
+    def _stats(self, stage: str) -> dict:
+        """A tallied stage's row count and sums over all its holders, as Python
+        ints. Pending sub-batches are replaced first; synchronises."""
+        need, count, _, names, _ = _TALLIED[stage]
+        if stage not in self.on:
+            raise ValueError(f"{stage}_stats() needs Island({need})")
+        self.flush()
+        self.sync()
+        holders = [t[stage] for t in [self._init_tally] + [p.tally for p in self._parts] if stage in t]
+        totals = sum(t.sums.cpu() for t in holders).tolist()
+        return {count: sum(t.rows for t in holders), **{k: int(v) for k, v in zip(names, totals)}}
+
+    def cx_stats(self) -> dict:
+        """Island(crossover="guided"): the children bred, how many of them
+        crossed, how many of those came out with cost 0, and the cost and the
+        repaired events summed over the crossed children."""
+        return self._stats("cx")
 
     def lahc_stats(self) -> dict:
         """Island(lahc > 0): the rows tt_lahc was called on, how many of them
         were feasible at entry and walked, how many came back better, the
-        candidates accepted and the scv gained in all, as Python ints. Pending
-        sub-batches are replaced first; synchronises."""
-        if not self.lahc > 0:
-            raise ValueError("lahc_stats() needs Island(lahc > 0)")
-        self.flush()
-        self.sync()
-        searched, improved, accepted, gain = (int(v) for v in sum(b.sums.cpu() for b in [self._lahc_init]
-                                                                  + [p.lahc for p in self._parts]).tolist())
-        return {"rows": int(self._lahc_rows), "searched": searched, "improved": improved, "accepted": accepted,
-                "gain": gain}
+        candidates accepted and the scv gained in all."""
+        return self._stats("lahc")
 
     def slot_swap_stats(self) -> dict:
         """Island(slot_swap > 0): the rows tt_slot_swap was called on, how many
-        of them it improved, the swaps applied and the scv gained in all, as
-        Python ints. Pending sub-batches are replaced first; synchronises."""
-        if not self.slot_swap > 0:
-            raise ValueError("slot_swap_stats() needs Island(slot_swap > 0)")
-        self.flush()
-        self.sync()
-        improved, passes, gain = (int(v) for v in sum(b.sums.cpu() for b in [self._swap_init]
-                                                      + [p.swap for p in self._parts]).tolist())
-        return {"rows": int(self._swap_rows), "improved": improved, "passes": passes, "gain": gain}
+        of them it improved, the swaps applied and the scv gained in all."""
+        return self._stats("slot_swap")
 
     def kempe_stats(self) -> dict:
         """Island(kempe > 0): the children tt_kempe_move was called on, how many
         of them moved a chain, how many chains the cap rejected, and the events
-        moved in all, as Python ints. Pending sub-batches are replaced first;
-        synchronises."""
-        if not self.kempe > 0:
-            raise ValueError("kempe_stats() needs Island(kempe > 0)")
-        self.flush()
-        self.sync()
-        moved, rejected, events = (int(v) for v in sum(p.kempe_sums.cpu() for p in self._parts).tolist())
-        return {"children": int(self._kempe_children), "moved": moved, "rejected": rejected, "chain_events": events}
+        moved in all."""
+        return self._stats("kempe")
 
     def _replace_oldest(self):
         j = self._pending.pop(0)
@@ -867,3 +833,15 @@ def crossover_line(stats: dict) -> str:
 def run_final_line(procs: int, threads: int, total_time: float) -> str:
     """main's closing runEntry (ga.cpp:603-609)."""
     return json_line({"runEntry": {"procsNum": int(procs), "threadsNum": int(threads), "totalTime": float(total_time)}})
+
+
+# The drivers' stage lines in print order: the stage (Island.on), whether its line follows
+# the island's solution line directly (the others come behind all solution lines, stage by
+# stage), and the line of island `isl` with global id `proc` and index `k` in its process
+STAGE_LINES = (
+    ("cx", True, lambda isl, proc, k: crossover_line(isl.cx_stats())),
+    ("kempe", True, lambda isl, proc, k: kempe_line(isl.kempe_stats())),
+    ("unique", False, lambda isl, proc, k: unique_line(isl.unique_stats(), proc, k)),
+    ("slot_swap", False, lambda isl, proc, k: slot_swap_line(isl.slot_swap_stats())),
+    ("lahc", False, lambda isl, proc, k: lahc_line(isl.lahc_stats())),
+)

@@ -75,6 +75,8 @@ import os
 import sys
 import time
 
+from . import stages
+
 USAGE = "-i InputFile [-o OutputFile] [-n NumberOfTries] [-s RandomSeed] [-t TimeLimit] [-p ProblemType]"
 TOTAL_CHILDREN = 2001          # generations 0..2000 per rank, ga.cpp:510
 
@@ -89,83 +91,18 @@ def parse_control(argv, out=sys.stdout, err=sys.stderr) -> dict:
     if "--report" in args:                # a population report line per island (ttga.report)
         args.remove("--report")
         extra["report"] = True
-    if "--unique" in args:                # duplicate-free replacement (include/ttga_unique.h)
-        args.remove("--unique")
-        extra["unique"] = True
     for k in ("--pop", "--children", "--generations", "--islands", "--stagger-parts"):
         if k in args:
             i = args.index(k)
             extra[k[2:].replace("-", "_")] = int(args[i + 1])
             del args[i:i + 2]
-    if "--init" in args:                  # the initial population (include/ttga_greedy.h)
-        i = args.index("--init")
-        if i + 1 >= len(args) or args[i + 1] not in ("random", "greedy"):
-            err.write("Error: --init must be random or greedy\n")
-            raise SystemExit(1)
-        extra["init"] = args[i + 1]
-        del args[i:i + 2]
-    for k, conv in (("--kempe", float), ("--kempe-max-chain", int)):     # include/ttga_kempe.h
-        if k in args:
-            i = args.index(k)
-            try:
-                v = conv(args[i + 1])
-            except (IndexError, ValueError):
-                v = -1
-            if not (v >= 0 and (conv is int or v <= 1)):     # a NaN fails both
-                err.write("Error: --kempe must be a probability in [0, 1], --kempe-max-chain an integer >= 0\n")
-                raise SystemExit(1)
-            extra[k[2:].replace("-", "_")] = v
-            del args[i:i + 2]
-    if "--slot-swap" in args:             # include/ttga_slotswap.h
-        i = args.index("--slot-swap")
-        try:
-            v = int(args[i + 1])
-        except (IndexError, ValueError):
-            v = -1
-        if not 0 <= v <= 2 ** 31 - 1:
-            err.write("Error: --slot-swap must be a non-negative integer\n")
-            raise SystemExit(1)
-        extra["slot_swap"] = v
-        del args[i:i + 2]
-    for flag, key, low, what in (("--lahc", "lahc", 0, "a non-negative integer"),
-                                 ("--lahc-history", "lahc_history", 1, "a positive integer")):   # include/ttga_lahc.h
-        if flag in args:
-            i = args.index(flag)
-            try:
-                v = int(args[i + 1])
-            except (IndexError, ValueError):
-                v = -1
-            if not low <= v <= 2 ** 31 - 1:
-                err.write(f"Error: {flag} must be {what}\n")
-                raise SystemExit(1)
-            extra[key] = v
-            del args[i:i + 2]
-    if "--lahc-swap" in args:
-        i = args.index("--lahc-swap")
-        try:
-            v = float(args[i + 1])
-        except (IndexError, ValueError):
-            v = -1.0
-        if not 0.0 <= v <= 1.0:             # a NaN fails
-            err.write("Error: --lahc-swap must be a probability in [0, 1]\n")
-            raise SystemExit(1)
-        extra["lahc_swap"] = v
-        del args[i:i + 2]
-    repair = "--crossover-repair" in args   # include/ttga_cx.h
-    if repair:
-        args.remove("--crossover-repair")
-    if "--crossover" in args:
-        i = args.index("--crossover")
-        if i + 1 >= len(args) or args[i + 1] not in ("uniform", "guided"):
-            err.write("Error: --crossover must be uniform or guided\n")
-            raise SystemExit(1)
-        extra["crossover"] = args[i + 1]
-        del args[i:i + 2]
-    if repair:
-        if extra.get("crossover") != "guided":
-            err.write("Error: --crossover-repair needs --crossover guided\n")
-            raise SystemExit(1)
-        extra["crossover_repair"] = True
+    for f in stages.FLAGS:                # the optional stages: an absent flag stays an absent key
+        v = stages.take(args, f, err)
+        if v is not None:
+            extra[f.key] = v
+    if extra.get("crossover_repair") and extra.get("crossover") != "guided":
+        err.write("Error: --crossover-repair needs --crossover guided\n")
+        raise SystemExit(1)
     if len(args) % 2 != 0:
         err.write("Parse error: Number of command line parameters incorrect\nUsage:\n" + USAGE + "\n")
         raise SystemExit(1)
@@ -307,8 +244,7 @@ def main(argv=None):
     import torch.distributed as dist
 
     from . import instance as tim
-    from .ga import (CostLog, Island, crossover_line, kempe_line, lahc_line, max_steps_for, run_best_line, run_final_line, slot_swap_line,
-                     solution_line, unique_line)
+    from .ga import STAGE_LINES, CostLog, Island, max_steps_for, run_best_line, run_final_line, solution_line
 
     from .native import DeviceProblem
 
@@ -360,11 +296,7 @@ def main(argv=None):
     islands = [Island(dp, pop_size=N, children=C, max_steps=max_steps_for(ctl["problem_type"]),
                       seed=rank_seed(seed, rank * K + k), p1=ctl["p1"], p2=ctl["p2"], p3=ctl["p3"],
                       stream=streams[k], schedule="staggered" if parts >= 2 else "batch", parts=max(parts, 2),
-                      unique=bool(ctl.get("unique")), init=ctl.get("init", "random"),
-                      kempe=ctl.get("kempe", 0.0), kempe_max_chain=ctl.get("kempe_max_chain", 0),
-                      slot_swap=ctl.get("slot_swap", 0), lahc=ctl.get("lahc", 0),
-                      lahc_history=ctl.get("lahc_history", 500), lahc_swap=ctl.get("lahc_swap", 0.5),
-                      crossover=ctl.get("crossover", "uniform"), crossover_repair=bool(ctl.get("crossover_repair")))
+                      **{key: ctl[key] for key in stages.KEYS if key in ctl})     # the rest: Island's defaults
                for k in range(K)]
     if rank == 0:
         islands[0].initialize()
@@ -410,19 +342,13 @@ def main(argv=None):
         out.write(run_best_line(vals[0][0], gmin) + "\n")
     for k, isl in enumerate(islands):
         out.write(solution_line(isl.member(0), rank * K + k, time.perf_counter() - t_begin) + "\n")
-        if ctl.get("crossover") == "guided":
-            out.write(crossover_line(isl.cx_stats()) + "\n")
-        if ctl.get("kempe", 0.0) > 0:
-            out.write(kempe_line(isl.kempe_stats()) + "\n")
-    if ctl.get("unique"):
+        for stage, after_solution, line in STAGE_LINES:
+            if after_solution and stage in isl.on:
+                out.write(line(isl, rank * K + k, k) + "\n")
+    for stage, after_solution, line in STAGE_LINES:
         for k, isl in enumerate(islands):
-            out.write(unique_line(isl.unique_stats(), rank * K + k, k) + "\n")
-    if ctl.get("slot_swap", 0) > 0:
-        for isl in islands:
-            out.write(slot_swap_line(isl.slot_swap_stats()) + "\n")
-    if ctl.get("lahc", 0) > 0:
-        for isl in islands:
-            out.write(lahc_line(isl.lahc_stats()) + "\n")
+            if not after_solution and stage in isl.on:
+                out.write(line(isl, rank * K + k, k) + "\n")
     if ctl.get("report"):
         from .report import report_line
         for k, isl in enumerate(islands):

@@ -73,7 +73,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import ttga  # noqa: E402
-from ttga import native  # noqa: E402
+from ttga import native, stages  # noqa: E402
 from ttga.ga import Island  # noqa: E402
 
 sys.path.insert(0, str(REPO))
@@ -108,22 +108,7 @@ def parser():
     ap.add_argument("--islands", type=int, default=1,
                     help="K independent islands of --pop members on this GPU, each on its own stream (ttga.islands "
                          "--islands K between migrations); children/s over all K")
-    ap.add_argument("--unique", action="store_true", help="duplicate-free replacement (Island(unique=True))")
-    ap.add_argument("--init", choices=["random", "greedy"], default="random",
-                    help="the initial population: tt_random_init or tt_greedy_init (Island(init=...))")
-    ap.add_argument("--kempe", type=float, default=0.0,
-                    help="probability of tt_kempe_move per child (Island(kempe=...)); 0: never called")
-    ap.add_argument("--kempe-max-chain", type=int, default=0, help="the cap on a chain's length (0: none)")
-    ap.add_argument("--slot-swap", type=int, default=0,
-                    help="max_passes of tt_slot_swap behind every search (Island(slot_swap=...)); 0: never called")
-    ap.add_argument("--lahc", type=int, default=0,
-                    help="steps of tt_lahc behind every search (Island(lahc=...)); 0: never called")
-    ap.add_argument("--lahc-history", type=int, default=500, help="tt_lahc's history length")
-    ap.add_argument("--lahc-swap", type=float, default=0.5, help="tt_lahc's share of Move2 candidates")
-    ap.add_argument("--crossover", choices=["uniform", "guided"], default="uniform",
-                    help="the breeding operator: tt_ga_breed or tt_ga_breed_guided (Island(crossover=...))")
-    ap.add_argument("--crossover-repair", action="store_true",
-                    help="guided: an event that clashes in both parents' slots goes to a slot of least cost")
+    stages.add_arguments(ap)
     return ap
 
 
@@ -136,10 +121,7 @@ def run_ga(a):
     seeds = [a.seed] + [rank_seed(a.seed, k) for k in range(1, K)]
     isls = [Island(dp, pop_size=a.pop, children=a.children, max_steps=a.steps, seed=seeds[k],
                    lpt=None if a.lpt == "auto" else a.lpt == "on", stream=torch.cuda.Stream() if K > 1 else None,
-                   schedule=a.schedule, parts=a.parts, unique=a.unique, init=a.init, kempe=a.kempe,
-                   kempe_max_chain=a.kempe_max_chain, slot_swap=a.slot_swap, lahc=a.lahc,
-                   lahc_history=a.lahc_history, lahc_swap=a.lahc_swap, crossover=a.crossover,
-                   crossover_repair=a.crossover_repair)
+                   schedule=a.schedule, parts=a.parts, **stages.island_kwargs(a))
             for k in range(K)]
     isl = isls[0]
     torch.cuda.synchronize()

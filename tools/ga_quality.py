@@ -60,6 +60,7 @@ cost 0, the cost and the events repaired. With --lahc N / --slot-swap M both
 islands run them and only the crossover differs.
 """
 import argparse
+import functools
 import json
 import os
 import pathlib
@@ -72,6 +73,7 @@ sys.path.insert(0, str(REPO / "tests"))
 import numpy as np  # noqa: E402
 
 import ttga  # noqa: E402
+from ttga import stages  # noqa: E402
 
 
 def summarize(final, feas, trace, checkpoints):
@@ -91,18 +93,16 @@ def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch", uni
                 lahc_swap=0.5, crossover="uniform", crossover_repair=False):
     import torch
 
-    from ttga import native
+    from ttga import native, stages
     from ttga.ga import Island
+    stage_kw = {k: v for k, v in locals().items() if k in stages.KEYS}
     dp = native.DeviceProblem(inst)
     final = np.zeros(len(seeds), np.int64)
     feas = np.zeros(len(seeds), np.uint8)
     trace = np.zeros((len(seeds), gens + 1), np.int64)
     secs = []
     for k, s in enumerate(seeds):
-        isl = Island(dp, pop_size=pop, children=children, max_steps=steps, seed=int(s), schedule=schedule,
-                     unique=unique, init=init, kempe=kempe, kempe_max_chain=kempe_max_chain,
-                     slot_swap=slot_swap, lahc=lahc, lahc_history=lahc_history, lahc_swap=lahc_swap,
-                     crossover=crossover, crossover_repair=crossover_repair)
+        isl = Island(dp, pop_size=pop, children=children, max_steps=steps, seed=int(s), schedule=schedule, **stage_kw)
         tr = torch.zeros(gens + 1, dtype=torch.int64, device="cuda")
         p = isl.pop
 
@@ -125,20 +125,44 @@ def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch", uni
         feas[k] = 1 if isl.member_meta(0)[0] else 0
         final[k] = trace[k, -1]
         if stats_out is not None:
-            if crossover == "guided":
-                stats_out.append(isl.cx_stats())
-            elif lahc > 0:
-                stats_out.append(isl.lahc_stats())
-            elif slot_swap > 0:
-                stats_out.append(isl.slot_swap_stats())
-            elif kempe > 0:
-                stats_out.append(isl.kempe_stats())
-            elif unique:
-                stats_out.append(isl.unique_stats())
+            stage = next((s for s in ("cx", "lahc", "slot_swap", "kempe", "unique") if s in isl.on), None)
+            if stage:        # the first of these that is on
+                stats_out.append(getattr(isl, stage + "_stats")())
             else:            # the plain island's distinct genomes, for the comparison
                 first = dp.genome_first(isl.pop["slot"], isl.pop["room"])
                 stats_out.append({"distinct": int((first == torch.arange(pop, dtype=torch.int32, device="cuda")).sum())})
     return final, feas, trace, float(np.mean(secs))
+
+
+def ab_compare(a, res, inst, seeds, names, kws, test, medians, extras=None, plain_stats=False, early=(1, 10, 100)):
+    """The device GA against itself, same seeds and parameters, no reference
+    run: res["runs"][names[0]] without a stage (Island keywords kws[0]) and
+    res["runs"][names[1]] with it (kws[1]), then res["tests"][test]: the final
+    values' Mann-Whitney U (two-sided) and their medians under the names
+    medians = (with, without). extras(stats, with_stage) turns a run's per-seed
+    stats into further keys of its record: asked for the run with the stage, and
+    with plain_stats for the other too. The logged best is kept at generations
+    0, `early`, half way and at the end. Prints the record and writes --out."""
+    from scipy import stats
+    dg = a.device_gens or a.gens
+    res["children_per_generation"], res["generations"] = a.device_children, dg
+    cps = sorted({0, *early, dg // 2, dg} & set(range(dg + 1)))
+    for name, kw, with_stage in zip(names, kws, (False, True)):
+        st = [] if extras and (with_stage or plain_stats) else None
+        final, feas, trace, secs = device_runs(inst, seeds, a.pop, dg, a.steps, a.device_children, a.device_schedule,
+                                               stats_out=st, **kw)
+        res["runs"][name] = summarize(final, feas, trace, cps)
+        res["runs"][name]["seconds_per_run"] = secs
+        if st:
+            res["runs"][name].update(extras(st, with_stage))
+    vp, vw = (np.array(res["runs"][n]["final_log_value"]) for n in names)
+    same = bool(np.array_equal(vp, vw))
+    res["tests"] = {test: {
+        "final_value_mannwhitney_p": 1.0 if same else float(stats.mannwhitneyu(vw, vp, alternative="two-sided").pvalue),
+        medians[0]: float(np.median(vw)), medians[1]: float(np.median(vp))}}
+    print(json.dumps(res), flush=True)
+    if a.out:
+        pathlib.Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
 
 
 def main():
@@ -155,22 +179,15 @@ def main():
     ap.add_argument("--device-gens", type=int, default=0, help="device generations (0: --gens)")
     ap.add_argument("--device-schedule", choices=["batch", "staggered"], default="batch")
     ap.add_argument("--no-ref-as-is", action="store_true", help="skip the reference run with F2")
-    ap.add_argument("--unique", action="store_true",
-                    help="compare Island(unique=True) with the plain island (no reference run)")
-    ap.add_argument("--init", choices=["random", "greedy"], default="random",
-                    help="greedy: compare Island(init='greedy') with the plain island (no reference run)")
-    ap.add_argument("--kempe", type=float, default=0.0,
-                    help="P > 0: compare Island(kempe=P) with the plain island (no reference run)")
-    ap.add_argument("--kempe-max-chain", type=int, default=0, help="the cap on a chain's length (0: none)")
-    ap.add_argument("--slot-swap", type=int, default=0,
-                    help="N > 0: compare Island(slot_swap=N) with the plain island (no reference run)")
-    ap.add_argument("--lahc", type=int, default=0,
-                    help="N > 0: compare Island(lahc=N) with the island without it (no reference run)")
-    ap.add_argument("--lahc-history", type=int, default=500)
-    ap.add_argument("--lahc-swap", type=float, default=0.5)
-    ap.add_argument("--crossover", choices=["uniform", "guided"], default="uniform",
-                    help="guided: compare Island(crossover='guided') with the island without it (no reference run)")
-    ap.add_argument("--crossover-repair", action="store_true")
+    plain, without = "with the plain island (no reference run)", "with the island without it (no reference run)"
+    stages.add_arguments(ap, help={
+        "unique": f"compare Island(unique=True) {plain}",
+        "init": f"greedy: compare Island(init='greedy') {plain}",
+        "kempe": f"P > 0: compare Island(kempe=P) {plain}",
+        "slot_swap": f"N > 0: compare Island(slot_swap=N) {plain}",
+        "lahc": f"N > 0: compare Island(lahc=N) {without}",
+        "crossover": f"guided: compare Island(crossover='guided') {without}",
+        "lahc_history": None, "lahc_swap": None, "crossover_repair": None})
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     from scipy import stats
@@ -194,150 +211,56 @@ def main():
            "runs": {}}
     if a.crossover_repair and a.crossover != "guided":
         raise SystemExit("--crossover-repair needs --crossover guided")
+    run = functools.partial(ab_compare, a, res, inst, seeds)
+    rest = {"lahc": a.lahc, "lahc_history": a.lahc_history, "lahc_swap": a.lahc_swap, "slot_swap": a.slot_swap}
     if a.crossover == "guided":
-        dg = a.device_gens or a.gens
-        res["children_per_generation"], res["generations"] = a.device_children, dg
         res["crossover"], res["crossover_repair"] = a.crossover, bool(a.crossover_repair)
-        res["lahc"], res["lahc_history"], res["lahc_swap"], res["slot_swap"] = a.lahc, a.lahc_history, a.lahc_swap, a.slot_swap
-        cps = sorted({0, 1, 10, 100, dg // 2, dg} & set(range(dg + 1)))
-        for name, cx in (("device", "uniform"), ("device_guided", "guided")):
-            st = [] if cx == "guided" else None
-            final, feas, trace, secs = device_runs(inst, seeds, a.pop, dg, a.steps, a.device_children,
-                                                   a.device_schedule, stats_out=st, slot_swap=a.slot_swap, lahc=a.lahc,
-                                                   lahc_history=a.lahc_history, lahc_swap=a.lahc_swap, crossover=cx,
-                                                   crossover_repair=a.crossover_repair and cx == "guided")
-            res["runs"][name] = summarize(final, feas, trace, cps)
-            res["runs"][name]["seconds_per_run"] = secs
-            if st:
-                res["runs"][name]["cx_stats"] = st
-                crossed = sum(s["crossed"] for s in st)
-                res["runs"][name]["clean_share"] = sum(s["clean"] for s in st) / max(1, crossed)
-                res["runs"][name]["mean_cost"] = sum(s["cost"] for s in st) / max(1, crossed)
-                res["runs"][name]["mean_repaired"] = sum(s["repaired"] for s in st) / max(1, crossed)
-        vp, vg = (np.array(res["runs"][n]["final_log_value"]) for n in ("device", "device_guided"))
-        same = bool(np.array_equal(vp, vg))
-        res["tests"] = {"guided_vs_uniform": {
-            "final_value_mannwhitney_p": 1.0 if same else float(stats.mannwhitneyu(vg, vp, alternative="two-sided").pvalue),
-            "median_guided": float(np.median(vg)), "median_uniform": float(np.median(vp))}}
-        print(json.dumps(res), flush=True)
-        if a.out:
-            pathlib.Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
-        return
+        res.update(rest)
+
+        def extras(st, _):
+            crossed = max(1, sum(s["crossed"] for s in st))
+            return {"cx_stats": st, "clean_share": sum(s["clean"] for s in st) / crossed,
+                    "mean_cost": sum(s["cost"] for s in st) / crossed,
+                    "mean_repaired": sum(s["repaired"] for s in st) / crossed}
+        return run(("device", "device_guided"),
+                   (rest, dict(rest, crossover="guided", crossover_repair=a.crossover_repair)),
+                   "guided_vs_uniform", ("median_guided", "median_uniform"), extras)
     if a.unique:
-        dg = a.device_gens or a.gens
-        res["children_per_generation"], res["generations"] = a.device_children, dg
-        for name, uniq in (("device", False), ("device_unique", True)):
-            st = []
-            final, feas, trace, secs = device_runs(inst, seeds, a.pop, dg, a.steps, a.device_children,
-                                                   a.device_schedule, uniq, st)
-            res["runs"][name] = summarize(final, feas, trace, sorted({0, dg // 2, dg}))
-            res["runs"][name]["seconds_per_run"] = secs
-            res["runs"][name]["distinct"] = [s["distinct"] for s in st]
-            if uniq:
-                res["runs"][name]["dropped"] = [s["dropped"] for s in st]
-                res["runs"][name]["children"] = st[0]["children"]
-        vp, vu = (np.array(res["runs"][n]["final_log_value"]) for n in ("device", "device_unique"))
-        same = bool(np.array_equal(vp, vu))
-        res["tests"] = {"unique_vs_plain": {
-            "final_value_mannwhitney_p": 1.0 if same else float(stats.mannwhitneyu(vu, vp, alternative="two-sided").pvalue),
-            "median_unique": float(np.median(vu)), "median_plain": float(np.median(vp))}}
-        print(json.dumps(res), flush=True)
-        if a.out:
-            pathlib.Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
-        return
+        def extras(st, with_stage):
+            d = {"distinct": [s["distinct"] for s in st]}
+            return dict(d, dropped=[s["dropped"] for s in st], children=st[0]["children"]) if with_stage else d
+        return run(("device", "device_unique"), ({"unique": False}, {"unique": True}), "unique_vs_plain",
+                   ("median_unique", "median_plain"), extras, plain_stats=True, early=())
     if a.init == "greedy":
-        dg = a.device_gens or a.gens
-        res["children_per_generation"], res["generations"] = a.device_children, dg
-        cps = sorted({0, 1, 10, 100, dg // 2, dg} & set(range(dg + 1)))
-        for name, init in (("device", "random"), ("device_greedy", "greedy")):
-            final, feas, trace, secs = device_runs(inst, seeds, a.pop, dg, a.steps, a.device_children,
-                                                   a.device_schedule, init=init)
-            res["runs"][name] = summarize(final, feas, trace, cps)
-            res["runs"][name]["seconds_per_run"] = secs
-        vp, vg = (np.array(res["runs"][n]["final_log_value"]) for n in ("device", "device_greedy"))
-        same = bool(np.array_equal(vp, vg))
-        res["tests"] = {"greedy_vs_random": {
-            "final_value_mannwhitney_p": 1.0 if same else float(stats.mannwhitneyu(vg, vp, alternative="two-sided").pvalue),
-            "median_greedy": float(np.median(vg)), "median_random": float(np.median(vp))}}
-        print(json.dumps(res), flush=True)
-        if a.out:
-            pathlib.Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
-        return
+        return run(("device", "device_greedy"), ({"init": "random"}, {"init": "greedy"}), "greedy_vs_random",
+                   ("median_greedy", "median_random"))
     if a.kempe > 0:
-        dg = a.device_gens or a.gens
-        res["children_per_generation"], res["generations"] = a.device_children, dg
         res["kempe"], res["kempe_max_chain"] = a.kempe, a.kempe_max_chain
-        cps = sorted({0, 1, 10, 100, dg // 2, dg} & set(range(dg + 1)))
-        for name, prob in (("device", 0.0), ("device_kempe", a.kempe)):
-            st = [] if prob > 0 else None
-            final, feas, trace, secs = device_runs(inst, seeds, a.pop, dg, a.steps, a.device_children,
-                                                   a.device_schedule, stats_out=st, kempe=prob,
-                                                   kempe_max_chain=a.kempe_max_chain)
-            res["runs"][name] = summarize(final, feas, trace, cps)
-            res["runs"][name]["seconds_per_run"] = secs
-            if st:
-                res["runs"][name]["kempe_stats"] = st
-                moved, events = sum(s["moved"] for s in st), sum(s["chain_events"] for s in st)
-                res["runs"][name]["mean_chain"] = events / moved if moved else 0.0
-        vp, vk = (np.array(res["runs"][n]["final_log_value"]) for n in ("device", "device_kempe"))
-        same = bool(np.array_equal(vp, vk))
-        res["tests"] = {"kempe_vs_plain": {
-            "final_value_mannwhitney_p": 1.0 if same else float(stats.mannwhitneyu(vk, vp, alternative="two-sided").pvalue),
-            "median_kempe": float(np.median(vk)), "median_plain": float(np.median(vp))}}
-        print(json.dumps(res), flush=True)
-        if a.out:
-            pathlib.Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
-        return
+
+        def extras(st, _):
+            moved, events = sum(s["moved"] for s in st), sum(s["chain_events"] for s in st)
+            return {"kempe_stats": st, "mean_chain": events / moved if moved else 0.0}
+        cap = {"kempe_max_chain": a.kempe_max_chain}
+        return run(("device", "device_kempe"), (dict(cap, kempe=0.0), dict(cap, kempe=a.kempe)), "kempe_vs_plain",
+                   ("median_kempe", "median_plain"), extras)
     if a.lahc > 0:
-        dg = a.device_gens or a.gens
-        res["children_per_generation"], res["generations"] = a.device_children, dg
-        res["lahc"], res["lahc_history"], res["lahc_swap"], res["slot_swap"] = a.lahc, a.lahc_history, a.lahc_swap, a.slot_swap
-        cps = sorted({0, 1, 10, 100, dg // 2, dg} & set(range(dg + 1)))
-        for name, n in (("device", 0), ("device_lahc", a.lahc)):
-            st = [] if n > 0 else None
-            final, feas, trace, secs = device_runs(inst, seeds, a.pop, dg, a.steps, a.device_children,
-                                                   a.device_schedule, stats_out=st, slot_swap=a.slot_swap, lahc=n,
-                                                   lahc_history=a.lahc_history, lahc_swap=a.lahc_swap)
-            res["runs"][name] = summarize(final, feas, trace, cps)
-            res["runs"][name]["seconds_per_run"] = secs
-            if st:
-                res["runs"][name]["lahc_stats"] = st
-                res["runs"][name]["searched_share"] = sum(s["searched"] for s in st) / max(1, sum(s["rows"] for s in st))
-                res["runs"][name]["improved_share"] = sum(s["improved"] for s in st) / max(1, sum(s["rows"] for s in st))
-        vp, vs = (np.array(res["runs"][n]["final_log_value"]) for n in ("device", "device_lahc"))
-        same = bool(np.array_equal(vp, vs))
-        res["tests"] = {"lahc_vs_without": {
-            "final_value_mannwhitney_p": 1.0 if same else float(stats.mannwhitneyu(vs, vp, alternative="two-sided").pvalue),
-            "median_lahc": float(np.median(vs)), "median_without": float(np.median(vp))}}
-        print(json.dumps(res), flush=True)
-        if a.out:
-            pathlib.Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
-        return
+        res.update(rest)
+
+        def extras(st, _):
+            rows = max(1, sum(s["rows"] for s in st))
+            return {"lahc_stats": st, "searched_share": sum(s["searched"] for s in st) / rows,
+                    "improved_share": sum(s["improved"] for s in st) / rows}
+        return run(("device", "device_lahc"), (dict(rest, lahc=0), rest), "lahc_vs_without",
+                   ("median_lahc", "median_without"), extras)
     if a.slot_swap > 0:
-        dg = a.device_gens or a.gens
-        res["children_per_generation"], res["generations"] = a.device_children, dg
         res["slot_swap"] = a.slot_swap
-        cps = sorted({0, 1, 10, 100, dg // 2, dg} & set(range(dg + 1)))
-        for name, n in (("device", 0), ("device_slot_swap", a.slot_swap)):
-            st = [] if n > 0 else None
-            final, feas, trace, secs = device_runs(inst, seeds, a.pop, dg, a.steps, a.device_children,
-                                                   a.device_schedule, stats_out=st, slot_swap=n)
-            res["runs"][name] = summarize(final, feas, trace, cps)
-            res["runs"][name]["seconds_per_run"] = secs
-            if st:
-                res["runs"][name]["slot_swap_stats"] = st
-                improved, passes = sum(s["improved"] for s in st), sum(s["passes"] for s in st)
-                res["runs"][name]["mean_passes"] = passes / improved if improved else 0.0
-                res["runs"][name]["improved_share"] = improved / max(1, sum(s["rows"] for s in st))
-        vp, vs = (np.array(res["runs"][n]["final_log_value"]) for n in ("device", "device_slot_swap"))
-        same = bool(np.array_equal(vp, vs))
-        res["tests"] = {"slot_swap_vs_plain": {
-            "final_value_mannwhitney_p": 1.0 if same else float(stats.mannwhitneyu(vs, vp, alternative="two-sided").pvalue),
-            "median_slot_swap": float(np.median(vs)), "median_plain": float(np.median(vp))}}
-        print(json.dumps(res), flush=True)
-        if a.out:
-            pathlib.Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
-        return
+
+        def extras(st, _):
+            improved, passes = sum(s["improved"] for s in st), sum(s["passes"] for s in st)
+            return {"slot_swap_stats": st, "mean_passes": passes / improved if improved else 0.0,
+                    "improved_share": improved / max(1, sum(s["rows"] for s in st))}
+        return run(("device", "device_slot_swap"), ({"slot_swap": 0}, {"slot_swap": a.slot_swap}),
+                   "slot_swap_vs_plain", ("median_slot_swap", "median_plain"), extras)
     R = ref()
     if R is None:
         raise SystemExit("oracle/_ref/libttref.so is missing (build it where /root/reference exists)")
