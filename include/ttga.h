@@ -35,7 +35,8 @@
  * between two timeslots), ttga_slotswap.h (the timeslot-swap descent: two
  * whole timeslots trade their events while that lowers scv), ttga_lahc.h
  * (late-acceptance hill climbing over feasible rows: single-event moves that
- * keep hcv 0, the best row seen comes back) and ttga_cx.h (a conflict-guided
+ * keep hcv 0, the best row seen comes back; it brings in ttga_lahc_kempe.h,
+ * the same walk with Kempe chains among its candidates) and ttga_cx.h (a conflict-guided
  * crossover: each event takes the parent's slot that clashes less with what
  * the child holds already, and a breed call built on it).
  */
@@ -249,8 +250,8 @@ int tt_ga_replace(const tt_problem* p, uint8_t* pop_slot, uint8_t* pop_room, int
  *              a room gene >= R untouched;
  *   bit 7 (128) ttga_slotswap.h's tt_slot_swap left a row with a slot gene >= 45
  *              untouched;
- *   bit 8 (256) ttga_lahc.h's tt_lahc left a row with a slot gene >= 45 or a room
- *              gene >= R untouched;
+ *   bit 8 (256) ttga_lahc.h's tt_lahc or tt_lahc_kempe left a row with a slot
+ *              gene >= 45 or a room gene >= R untouched;
  *   bit 9 (512) ttga_cx.h's tt_crossover_guided or tt_ga_breed_guided skipped an
  *              order entry outside 0..E-1.
  * Synchronises the device. */

@@ -101,4 +101,8 @@ int tt_lahc(const tt_problem* p, uint8_t* slot, uint8_t* room, int64_t* rng, int
 }
 #endif
 
+/* The same walk with Kempe-chain candidates as a third kind of move is
+ * declared in ttga_lahc_kempe.h, which this header brings in. */
+#include "ttga_lahc_kempe.h"
+
 #endif /* TTGA_LAHC_H */

@@ -13,33 +13,15 @@
 // one AND of its possible rooms with the slot's free rooms; no matcher runs.
 #include "../../include/ttga_lahc.h"
 #include "tt_internal.h"
+#include "tt_lahc_common.h"
 
 namespace ttga {
-
-constexpr int kStatusLahcBadGene = 256;     // tt_device_status bit 8
-constexpr size_t kLahcMaxLds = 64 * 1024;
 
 // LDS of one wave: set[45][EW64] u64 | occ[45] u64 | mask[S] u64 | hist[L] i32 |
 //                  sl[E] | rr[E] | bsl[E] | brr[E]  (u8)
 __host__ __device__ inline size_t lahc_lds_bytes(int E, int S, int L) {
     return 8 * ((size_t)kSlots * (size_t)((E + 63) / 64) + kSlots + (size_t)S) + 4 * (size_t)L + 4 * (size_t)E;
 }
-
-// one day's cost of a student: last slot of the day, windows of three, single class
-__device__ __forceinline__ int lahc_day_cost(uint64_t m, int day) {
-    const uint32_t d = (uint32_t)(m >> (9 * day)) & 0x1FFu;
-    return (int)(d >> 8) + __popc(d & (d >> 1) & (d >> 2)) + (__popc(d) == 1);
-}
-
-// cost(m ^ flip) - cost(m) where flip has bits on days da and db only
-__device__ __forceinline__ int lahc_mask_delta(uint64_t m, uint64_t flip, int da, int db) {
-    const uint64_t n = m ^ flip;
-    int d = lahc_day_cost(n, da) - lahc_day_cost(m, da);
-    if (db != da) d += lahc_day_cost(n, db) - lahc_day_cost(m, db);
-    return d;
-}
-
-__device__ __forceinline__ int lahc_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // One wave (workgroup) per individual. Everything that decides a step is wave-uniform:
 // every lane draws the same three numbers from its own copy of the state, and the

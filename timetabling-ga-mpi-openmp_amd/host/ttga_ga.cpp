@@ -13,6 +13,7 @@
 //           [-p1 x -p2 y -p3 z] [--gpus G] [--islands K] [--pop N] [--generations n] [--rccl] [--stagger]
 //           [--report] [--unique] [--init random|greedy] [--kempe P] [--kempe-max-chain N]
 //           [--slot-swap N] [--lahc N] [--lahc-history L] [--lahc-swap P]
+//           [--lahc-kempe P] [--lahc-kempe-max-chain N]
 //           [--crossover uniform|guided] [--crossover-repair]
 //
 // --crossover guided: every sub-batch is bred by tt_ga_breed_guided
@@ -32,6 +33,13 @@
 // and penalty lowered in place. Each island then prints one {"lahc": {"accepted",
 // "gain", "improved", "rows", "searched"}} line after the slotSwap line
 // (ttga.islands prints the same). The default is 0: no call.
+//
+// --lahc-kempe P (needs --lahc, and --lahc-swap + P <= 1): the walk is
+// tt_lahc_kempe (include/ttga_lahc_kempe.h) in place of tt_lahc, with a share P
+// of Kempe-chain candidates of at most --lahc-kempe-max-chain N events (0, the
+// default: no cap). Each island then prints one {"lahcKempe": {"accepted",
+// "capped", "meanChain", "noRoom", "tried"}} line after its lahc line
+// (ttga.islands prints the same). The default is 0: tt_lahc as before.
 //
 // --slot-swap N: tt_slot_swap (include/ttga_slotswap.h) with max_passes N runs
 // directly behind every tt_local_search_eval, on the same stream, and lowers
@@ -147,6 +155,8 @@ struct Stages {
     int lahc = 0;                                 // --lahc: tt_lahc's steps (0: never called)
     int lahc_history = 500;                       // --lahc-history
     double lahc_swap = 0.5;                       // --lahc-swap
+    double lahc_kempe = 0.0;                      // --lahc-kempe: tt_lahc_kempe's share of chains (0: tt_lahc)
+    int lahc_kempe_max_chain = 0;                 // --lahc-kempe-max-chain (0: no cap)
     bool guided = false;                          // --crossover guided: tt_ga_breed_guided breeds
     bool cx_repair = false;                       // --crossover-repair
 };
@@ -237,9 +247,15 @@ Control parse_control(int argc, char** argv) {
     take_int(args, "--lahc", 0, "--lahc must be a non-negative integer", s.lahc);
     take_int(args, "--lahc-history", 1, "--lahc-history must be a positive integer", s.lahc_history);
     take_prob(args, "--lahc-swap", "--lahc-swap must be a probability in [0, 1]", s.lahc_swap);
+    take_prob(args, "--lahc-kempe", "--lahc-kempe must be a probability in [0, 1]", s.lahc_kempe);
+    take_int(args, "--lahc-kempe-max-chain", 0, "--lahc-kempe-max-chain must be a non-negative integer",
+             s.lahc_kempe_max_chain);
     s.cx_repair = take_flag(args, "--crossover-repair");
     take_choice(args, "--crossover", "uniform", "guided", "--crossover must be uniform or guided", s.guided);
     if (s.cx_repair && !s.guided) bad_flag("--crossover-repair needs --crossover guided");
+    if (s.lahc_kempe > 0 && s.lahc <= 0) bad_flag("--lahc-kempe needs --lahc");
+    if (s.lahc_kempe > 0 && !(s.lahc_swap <= 1.0 - s.lahc_kempe))         // tt_lahc_kempe's own test
+        bad_flag("--lahc-swap and --lahc-kempe must not add up to more than 1");
     for (const char* k : {"--gpus", "--islands", "--pop", "--generations", "--children", "--stagger-parts"}) {
         auto it = std::find(args.begin(), args.end(), k);
         if (it != args.end()) {
@@ -669,6 +685,7 @@ struct Island {
     RunLog<1> chain_log;                              // --kempe: every child's chain length
     RunLog<2> swap_log;                               // --slot-swap: every searched row's gain and passes
     RunLog<2> lahc_log;                               // --lahc: every searched row's gain, accepted and feasible flag
+    RunLog<5> lk_log;                                 // --lahc-kempe: every searched row's five counts, row-major
     RunLog<2> cx_log;                                 // --crossover guided: every child's cost, repaired and flags
     int32_t* ev_order = nullptr;                      // event_order()'s, once computed
 
@@ -715,6 +732,7 @@ struct Island {
         if (stage.kempe > 0) chain_log.alloc(bred, "Kempe moves");
         if (stage.slot_swap > 0) swap_log.alloc(N + bred, "timeslot-swap rows");          // the members too
         if (stage.lahc > 0) lahc_log.alloc(N + bred, "late-acceptance rows", true);       // the members too
+        if (stage.lahc_kempe > 0) lk_log.alloc(N + bred, "late-acceptance rows");
         if (stage.guided) {
             cx_log.alloc(bred, "guided crossovers", true);
             event_order();                            // before any part's stream breeds in it
@@ -892,9 +910,17 @@ struct Island {
     // search, evaluation and timeslot swap; their scv and penalty are lowered in place
     void late_acceptance(const Pop& r, int64_t* g, hipStream_t s) {
         const long at = lahc_log.reserve(r.n);
-        check_tt(tt_lahc(tp, r.slot, r.room, g, r.n, stage.lahc, stage.lahc_history, stage.lahc_swap, r.scv, r.penalty,
-                         lahc_log.col(0) + at, lahc_log.col(1) + at, nullptr, s),
-                 "tt_lahc");
+        if (stage.lahc_kempe > 0) {
+            lk_log.reserve(r.n);                      // row for row with lahc_log
+            check_tt(tt_lahc_kempe(tp, r.slot, r.room, g, r.n, stage.lahc, stage.lahc_history, stage.lahc_swap,
+                                   stage.lahc_kempe, stage.lahc_kempe_max_chain, r.scv, r.penalty, lahc_log.col(0) + at,
+                                   lahc_log.col(1) + at, nullptr, lk_log.data + 5 * at, s),
+                     "tt_lahc_kempe");
+        } else {
+            check_tt(tt_lahc(tp, r.slot, r.room, g, r.n, stage.lahc, stage.lahc_history, stage.lahc_swap, r.scv,
+                             r.penalty, lahc_log.col(0) + at, lahc_log.col(1) + at, nullptr, s),
+                     "tt_lahc");
+        }
         check_hip(hipMemcpyAsync(lahc_log.bytes + at, r.feasible, (size_t)r.n, hipMemcpyDeviceToDevice, s),
                   "hipMemcpyAsync");
     }
@@ -916,6 +942,23 @@ struct Island {
         k.obj["accepted"] = Json::I(accepted);
         k.obj["gain"] = Json::I(total);
         return wrap("lahc", k);
+    }
+
+    // the --lahc-kempe line (ttga/ga.py lahc_kempe_line)
+    Json lahc_kempe_report() {
+        flush();
+        finish();
+        std::vector<int32_t> h(5 * (size_t)lk_log.used);
+        if (lk_log.used) check_hip(hipMemcpy(h.data(), lk_log.data, 4 * h.size(), hipMemcpyDeviceToHost), "hipMemcpy");
+        long sum[5] = {0, 0, 0, 0, 0};
+        for (size_t i = 0; i < h.size(); i++) sum[i % 5] += h[i];
+        Json k;
+        k.obj["tried"] = Json::I(sum[0]);
+        k.obj["capped"] = Json::I(sum[1]);
+        k.obj["noRoom"] = Json::I(sum[2]);
+        k.obj["accepted"] = Json::I(sum[3]);
+        k.obj["meanChain"] = Json::D(sum[3] ? (double)sum[4] / (double)sum[3] : 0.0);
+        return wrap("lahcKempe", k);
     }
 
     // LPT order (C >= kLptMinChildren), localSearch and evaluation of rows [off, off + n) on s
@@ -1106,6 +1149,7 @@ struct Island {
         chain_log.release();
         swap_log.release();
         lahc_log.release();
+        lk_log.release();
         cx_log.release();
         for (size_t j = 0; j < part.size(); j++) {
             if (part[j].work) (void)hipFree(part[j].work);
@@ -1297,6 +1341,7 @@ int main(int argc, char** argv) {
     each_island(ctl.stage.unique, [](Island& I, int k) { return I.unique_report(k, k); });
     each_island(ctl.stage.slot_swap > 0, [](Island& I, int) { return I.slot_swap_report(); });
     each_island(ctl.stage.lahc > 0, [](Island& I, int) { return I.lahc_report(); });
+    each_island(ctl.stage.lahc_kempe > 0, [](Island& I, int) { return I.lahc_kempe_report(); });
     each_island(ctl.report, [](Island& I, int k) { return I.report(k, k); });
     out.line(run_final_line(K, C, seconds_since(t_start)));
     for (int k = 0; k < K; k++) {

@@ -180,6 +180,8 @@ _TALLIED = {
     "kempe": ("kempe > 0", "children", ("chain",), ("moved", "rejected", "chain_events"), False),
     "slot_swap": ("slot_swap > 0", "rows", ("gain", "passes"), ("improved", "passes", "gain"), True),
     "lahc": ("lahc > 0", "rows", ("gain", "accepted", "best_step"), ("searched", "improved", "accepted", "gain"), True),
+    "lahc_kempe": ("lahc_kempe > 0", "rows", ("stats",), ("tried", "capped", "no_room", "accepted", "chain_events"),
+                   True),
     "cx": ("crossover='guided'", "children", ("cost", "repaired"), ("crossed", "clean", "cost", "repaired"), False),
 }
 
@@ -192,7 +194,7 @@ class Tally:
 
     def __init__(self, n: int, outputs, sums, dev, register: list):
         import torch
-        self.out = {k: torch.zeros(n, dtype=torch.int32, device=dev) for k in outputs}
+        self.out = {k: torch.zeros((n, 5) if k == "stats" else n, dtype=torch.int32, device=dev) for k in outputs}
         self.sums = torch.zeros(len(sums), dtype=torch.int64, device=dev)
         self.rows = 0
         register += [*self.out.values(), self.sums]
@@ -267,6 +269,14 @@ class Island(Members):
     rows that are feasible walk; their scv and penalty tensors are lowered in
     place. lahc=0 issues no call at all. lahc_stats() reports what the walks did.
 
+    lahc_kempe=p > 0 (needs lahc >= 1 and lahc_swap + p <= 1): the walk is
+    tt_lahc_kempe (include/ttga_lahc_kempe.h) in place of tt_lahc, at the same
+    places and with the same arguments: a share p of its candidates is a Kempe
+    chain between the event's slot and a second one, of at most
+    lahc_kempe_max_chain events (0: no cap). lahc_stats() counts all three
+    kinds of move; lahc_kempe_stats() reports the chains. lahc_kempe=0 calls
+    tt_lahc exactly as before.
+
     crossover="guided": every sub-batch is bred with tt_ga_breed_guided
     (include/ttga_cx.h) in place of tt_ga_breed, on the same stream and at the
     same place in the operation chain, in the handle's greedy_order(); with
@@ -275,7 +285,7 @@ class Island(Members):
     issues no new call at all. cx_stats() reports what the crossovers did.
 
     `on` is the set of these stages that are on: "unique", "kempe",
-    "slot_swap", "lahc", "cx" (the {stage}_stats() that do not raise).
+    "slot_swap", "lahc", "lahc_kempe", "cx" (the {stage}_stats() that do not raise).
     """
 
     def __init__(self, dp, pop_size: int = 10, children: int = 1, max_steps: int = 200, seed: int = 1,
@@ -284,14 +294,16 @@ class Island(Members):
                  schedule: str = "batch", parts: int = 2, unique: bool = False, init: str = "random",
                  kempe: float = 0.0, kempe_max_chain: int = 0, slot_swap: int = 0,
                  lahc: int = 0, lahc_history: int = 500, lahc_swap: float = 0.5,
-                 crossover: str = "uniform", crossover_repair: bool = False):
+                 crossover: str = "uniform", crossover_repair: bool = False,
+                 lahc_kempe: float = 0.0, lahc_kempe_max_chain: int = 0):
         """stream: a torch.cuda.Stream of the island's own, or None (torch's current
         stream). Islands multiplexed on one GPU (ttga.islands --islands K) each take
         one, so one island's launches fill the SIMD slots another's local-search tail
         leaves idle; every host read of the island (member, member_meta, best_thread)
         synchronises its stream first, and a caller that moves data between islands
         (migration) synchronises the device around it."""
-        validate(init, kempe, kempe_max_chain, slot_swap, lahc, lahc_history, lahc_swap, crossover, crossover_repair)
+        validate(init, kempe, kempe_max_chain, slot_swap, lahc, lahc_history, lahc_swap, crossover, crossover_repair,
+                 lahc_kempe, lahc_kempe_max_chain)
         import torch
         if not (1 <= children <= pop_size):
             raise ValueError("need 1 <= children <= pop_size")
@@ -317,6 +329,7 @@ class Island(Members):
         self.kempe, self.kempe_max_chain = float(kempe), int(kempe_max_chain)
         self.slot_swap = int(slot_swap)
         self.lahc, self.lahc_history, self.lahc_swap = int(lahc), int(lahc_history), float(lahc_swap)
+        self.lahc_kempe, self.lahc_kempe_max_chain = float(lahc_kempe), int(lahc_kempe_max_chain)
         self.crossover, self.crossover_repair = crossover, bool(crossover_repair)
         self.generation = 0
         self.schedule = schedule
@@ -357,6 +370,7 @@ class Island(Members):
         # stage also runs in initialize()
         self.on = {stage for stage, on in (("unique", self.unique), ("kempe", self.kempe > 0),
                                            ("slot_swap", self.slot_swap > 0), ("lahc", self.lahc > 0),
+                                           ("lahc_kempe", self.lahc_kempe > 0),
                                            ("cx", self.crossover == "guided")) if on}
         self._init_tally = {}
         for stage, (_, _, outputs, sums, in_init) in _TALLIED.items():
@@ -485,7 +499,7 @@ class Island(Members):
             if self.slot_swap > 0:
                 self._slot_swap(p, self._init_tally["slot_swap"])
             if self.lahc > 0:
-                self._lahc(p, self.rng_init, self._init_tally["lahc"])
+                self._lahc(p, self.rng_init, self._init_tally)
             if self.unique:
                 self.dp.ga_replace_unique(p, None, self.work, n_kept=self._init_kept)
             else:
@@ -536,7 +550,7 @@ class Island(Members):
             if self.slot_swap > 0:
                 self._slot_swap(p.child, p.tally["slot_swap"])
             if self.lahc > 0:
-                self._lahc(p.child, p.rng, p.tally["lahc"])
+                self._lahc(p.child, p.rng, p.tally)
             self._pending.append(j)
             if len(self._pending) >= self.parts:
                 self._replace_oldest()
@@ -569,15 +583,25 @@ class Island(Members):
                           passes=passes)
         t.add(int(rows["slot"].shape[0]), (passes > 0).sum(), passes.sum(), gain.sum())
 
-    def _lahc(self, rows, rng, t):
-        """tt_lahc on the searched rows (on the current stream, behind their
-        search and evaluation) and its counts, summed on the device behind the
-        call. The rows that walk are the feasible ones: the call's own gate is
-        tt_eval's hcv."""
+    def _lahc(self, rows, rng, tally):
+        """tt_lahc, or with lahc_kempe > 0 tt_lahc_kempe, on the searched rows
+        (on the current stream, behind their search and evaluation) and its
+        counts, summed on the device behind the call. The rows that walk are
+        the feasible ones: the call's own gate is tt_eval's hcv."""
+        t = tally["lahc"]
         gain, accepted = t.out["gain"], t.out["accepted"]
-        self.dp.lahc(rows["slot"], rows["room"], rng, self.lahc, self.lahc_history, self.lahc_swap, scv=rows["scv"],
-                     penalty=rows["penalty"], gain=gain, accepted=accepted, best_step=t.out["best_step"])
-        t.add(int(rows["slot"].shape[0]), (rows["feasible"] != 0).sum(), (gain > 0).sum(), accepted.sum(), gain.sum())
+        n = int(rows["slot"].shape[0])
+        if self.lahc_kempe > 0:
+            tk = tally["lahc_kempe"]
+            self.dp.lahc_kempe(rows["slot"], rows["room"], rng, self.lahc, self.lahc_history, self.lahc_swap,
+                               self.lahc_kempe, self.lahc_kempe_max_chain, scv=rows["scv"], penalty=rows["penalty"],
+                               gain=gain, accepted=accepted, best_step=t.out["best_step"], kempe_stats=tk.out["stats"])
+            tk.add(n, *tk.out["stats"].sum(dim=0).unbind())
+        else:
+            self.dp.lahc(rows["slot"], rows["room"], rng, self.lahc, self.lahc_history, self.lahc_swap,
+                         scv=rows["scv"], penalty=rows["penalty"], gain=gain, accepted=accepted,
+                         best_step=t.out["best_step"])
+        t.add(n, (rows["feasible"] != 0).sum(), (gain > 0).sum(), accepted.sum(), gain.sum())
 
     def _stats(self, stage: str) -> dict:
         """A tallied stage's row count and sums over all its holders, as Python
@@ -602,6 +626,12 @@ class Island(Members):
         were feasible at entry and walked, how many came back better, the
         candidates accepted and the scv gained in all."""
         return self._stats("lahc")
+
+    def lahc_kempe_stats(self) -> dict:
+        """Island(lahc_kempe > 0): the rows tt_lahc_kempe was called on, and of
+        their Kempe candidates those tried, capped, without a room and
+        accepted, and the events of the accepted chains."""
+        return self._stats("lahc_kempe")
 
     def slot_swap_stats(self) -> dict:
         """Island(slot_swap > 0): the rows tt_slot_swap was called on, how many
@@ -820,6 +850,15 @@ def lahc_line(stats: dict) -> str:
     return json_line({"lahc": {k: int(stats[k]) for k in ("accepted", "gain", "improved", "rows", "searched")}})
 
 
+def lahc_kempe_line(stats: dict) -> str:
+    """The drivers' --lahc-kempe line of one island: Island.lahc_kempe_stats()
+    with the mean length of the accepted chains (0 when there are none)."""
+    accepted = int(stats["accepted"])
+    return json_line({"lahcKempe": {"tried": int(stats["tried"]), "capped": int(stats["capped"]),
+                                    "noRoom": int(stats["no_room"]), "accepted": accepted,
+                                    "meanChain": float(stats["chain_events"]) / accepted if accepted else 0.0}})
+
+
 def crossover_line(stats: dict) -> str:
     """The drivers' --crossover guided line of one island: Island.cx_stats()
     with the mean cost of the crossed children (0 when none crossed)."""
@@ -844,4 +883,5 @@ STAGE_LINES = (
     ("unique", False, lambda isl, proc, k: unique_line(isl.unique_stats(), proc, k)),
     ("slot_swap", False, lambda isl, proc, k: slot_swap_line(isl.slot_swap_stats())),
     ("lahc", False, lambda isl, proc, k: lahc_line(isl.lahc_stats())),
+    ("lahc_kempe", False, lambda isl, proc, k: lahc_kempe_line(isl.lahc_kempe_stats())),
 )

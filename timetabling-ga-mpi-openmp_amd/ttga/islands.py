@@ -38,6 +38,12 @@ Reference correspondence:
   lahc_history=L, lahc_swap=P); each island then prints a `lahc` line after
   the slotSwap line: rows, rows searched, rows improved, candidates accepted,
   scv gained; 0: no call),
+  `--lahc-kempe P` / `--lahc-kempe-max-chain N` (0) (with --lahc N, and
+  --lahc-swap + P <= 1: the walk is tt_lahc_kempe, include/ttga_lahc_kempe.h,
+  with a share P of Kempe-chain candidates of at most N events,
+  ttga.ga.Island(lahc_kempe=P, lahc_kempe_max_chain=N); each island then prints
+  a `lahcKempe` line after the lahc line: chains tried, capped, without a
+  room, accepted, mean length of the accepted; 0: tt_lahc as before),
   `--crossover uniform|guided` / `--crossover-repair` (guided: the children are
   bred by tt_ga_breed_guided, include/ttga_cx.h, ttga.ga.Island(crossover=
   "guided", crossover_repair=...); each island then prints a `crossover` line
@@ -70,6 +76,7 @@ Reference correspondence:
 """
 from __future__ import annotations
 
+import inspect
 import math
 import os
 import sys
@@ -103,6 +110,14 @@ def parse_control(argv, out=sys.stdout, err=sys.stderr) -> dict:
     if extra.get("crossover_repair") and extra.get("crossover") != "guided":
         err.write("Error: --crossover-repair needs --crossover guided\n")
         raise SystemExit(1)
+    if "lahc_kempe" in extra:
+        from .ga import Island
+        d = inspect.signature(Island.__init__).parameters
+        message = stages.lahc_kempe_error(extra.get("lahc", d["lahc"].default),
+                                          extra.get("lahc_swap", d["lahc_swap"].default), extra["lahc_kempe"])
+        if message:
+            err.write(f"Error: {message}\n")
+            raise SystemExit(1)
     if len(args) % 2 != 0:
         err.write("Parse error: Number of command line parameters incorrect\nUsage:\n" + USAGE + "\n")
         raise SystemExit(1)

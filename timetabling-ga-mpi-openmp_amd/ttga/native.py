@@ -46,6 +46,9 @@ SLOTSWAP_EXPORTS = ("tt_slot_swap",)
 # include/ttga_lahc.h
 LAHC_EXPORTS = ("tt_lahc",)
 
+# include/ttga_lahc_kempe.h (brought in by ttga_lahc.h)
+LAHC_KEMPE_EXPORTS = ("tt_lahc_kempe",)
+
 # include/ttga_cx.h
 CX_EXPORTS = ("tt_crossover_guided", "tt_ga_breed_guided")
 
@@ -120,6 +123,8 @@ def load(path: os.PathLike | str | None = None) -> ctypes.CDLL:
     lib.tt_slot_swap.restype = ctypes.c_int
     lib.tt_lahc.argtypes = [vp, vp, vp, vp, i32, i32, i32, dbl, vp, vp, vp, vp, vp, vp]
     lib.tt_lahc.restype = ctypes.c_int
+    lib.tt_lahc_kempe.argtypes = [vp, vp, vp, vp, i32, i32, i32, dbl, dbl, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.tt_lahc_kempe.restype = ctypes.c_int
     lib.tt_crossover_guided.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]
     lib.tt_crossover_guided.restype = ctypes.c_int
     lib.tt_ga_breed_guided.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, dbl, dbl, i32, i32, vp, vp, vp, vp, vp, vp]
@@ -509,6 +514,29 @@ class DeviceProblem:
         _check(self.lib, self.lib.tt_lahc(self.handle, slot.data_ptr(), room.data_ptr(), rng.data_ptr(), P, int(steps),
                                           int(history), float(p_swap), ptr(scv), ptr(penalty), ptr(gain),
                                           ptr(accepted), ptr(best_step), self._stream(slot)))
+
+    def lahc_kempe(self, slot, room, rng, steps, history, p_swap=0.25, p_kempe=0.5, max_chain=0, scv=None, penalty=None,
+                   gain=None, accepted=None, best_step=None, kempe_stats=None):
+        """tt_lahc_kempe in place on slot, room [P, E] and rng [P]: tt_lahc's walk
+        in which a share p_kempe of the candidates is a Kempe chain between
+        e1's slot and a second one, of at most max_chain events (0: no cap),
+        with its rooms chosen directly; p_swap + p_kempe <= 1. The optional
+        tensors are lahc()'s, and kempe_stats (int32 [P, 5]: chains tried,
+        capped, without a room, accepted, and the events of the accepted ones)."""
+        import torch
+        P = self._pop(slot, room)
+        self._rng(rng, P)
+        for name, t, n in (("scv", scv, P), ("penalty", penalty, P), ("gain", gain, P), ("accepted", accepted, P),
+                           ("best_step", best_step, P), ("kempe_stats", kempe_stats, 5 * P)):
+            if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n
+                                      and t.device == slot.device):
+                raise ValueError(f"{name} must be a contiguous int32 CUDA tensor of {'5 P' if n != P else 'P'} entries "
+                                 "on the population's device")
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)    # noqa: E731
+        _check(self.lib, self.lib.tt_lahc_kempe(self.handle, slot.data_ptr(), room.data_ptr(), rng.data_ptr(), P,
+                                                int(steps), int(history), float(p_swap), float(p_kempe), int(max_chain),
+                                                ptr(scv), ptr(penalty), ptr(gain), ptr(accepted), ptr(best_step),
+                                                ptr(kempe_stats), self._stream(slot)))
 
     # -- conflict-guided crossover (include/ttga_cx.h) -------------------------------
     def _cx_args(self, slot, order, P, cost, repaired):

@@ -30,6 +30,11 @@ FLAGS = (
          "tt_lahc's history length"),
     Flag("--lahc-swap", "lahc_swap", "float", (0.0, 1.0), "--lahc-swap must be a probability in [0, 1]",
          "tt_lahc's share of Move2 candidates"),
+    Flag("--lahc-kempe", "lahc_kempe", "float", (0.0, 1.0), "--lahc-kempe must be a probability in [0, 1]",
+         "share of Kempe-chain candidates in the walk: tt_lahc_kempe in place of tt_lahc (Island(lahc_kempe=...)); "
+         "0: tt_lahc"),
+    Flag("--lahc-kempe-max-chain", "lahc_kempe_max_chain", "int", (0, INT_MAX),
+         "--lahc-kempe-max-chain must be a non-negative integer", "the cap on a chain's length in the walk (0: none)"),
     Flag("--crossover-repair", "crossover_repair", "flag", None, None,
          "guided: an event that clashes in both parents' slots goes to a slot of least cost"),
     Flag("--crossover", "crossover", "choice", ("uniform", "guided"), "--crossover must be uniform or guided",
@@ -38,7 +43,23 @@ FLAGS = (
 KEYS = tuple(f.key for f in FLAGS)
 
 
-def validate(init, kempe, kempe_max_chain, slot_swap, lahc, lahc_history, lahc_swap, crossover, crossover_repair):
+# what parse_control and the native driver say where --lahc-kempe does not go with the other --lahc flags
+LAHC_KEMPE_NEEDS_LAHC = "--lahc-kempe needs --lahc"
+LAHC_KEMPE_SHARES = "--lahc-swap and --lahc-kempe must not add up to more than 1"
+
+
+def lahc_kempe_error(lahc, lahc_swap, lahc_kempe):
+    """The message for a --lahc-kempe that does not go with --lahc and
+    --lahc-swap (the values in force, defaults included), or None."""
+    if lahc_kempe > 0 and lahc <= 0:
+        return LAHC_KEMPE_NEEDS_LAHC
+    if lahc_kempe > 0 and not lahc_swap <= 1.0 - lahc_kempe:          # tt_lahc_kempe's own test
+        return LAHC_KEMPE_SHARES
+    return None
+
+
+def validate(init, kempe, kempe_max_chain, slot_swap, lahc, lahc_history, lahc_swap, crossover, crossover_repair,
+             lahc_kempe=0.0, lahc_kempe_max_chain=0):
     """Island's stage arguments: the first one out of range raises ValueError."""
     for ok, message in (
             (crossover in ("uniform", "guided"), "crossover must be 'uniform' or 'guided'"),
@@ -49,7 +70,12 @@ def validate(init, kempe, kempe_max_chain, slot_swap, lahc, lahc_history, lahc_s
             (int(slot_swap) >= 0, "slot_swap must be >= 0 (0: off)"),
             (int(lahc) >= 0, "lahc must be >= 0 (0: off)"),
             (int(lahc_history) >= 1, "lahc_history must be >= 1"),
-            (0.0 <= float(lahc_swap) <= 1.0, "lahc_swap must be a probability in [0, 1]")):
+            (0.0 <= float(lahc_swap) <= 1.0, "lahc_swap must be a probability in [0, 1]"),
+            (0.0 <= float(lahc_kempe) <= 1.0, "lahc_kempe must be a probability in [0, 1]"),
+            (int(lahc_kempe_max_chain) >= 0, "lahc_kempe_max_chain must be >= 0 (0: no cap)"),
+            (not float(lahc_kempe) > 0 or int(lahc) > 0, "lahc_kempe > 0 needs lahc > 0"),
+            (not float(lahc_kempe) > 0 or float(lahc_swap) <= 1.0 - float(lahc_kempe),
+             "lahc_swap + lahc_kempe must be <= 1")):
         if not ok:
             raise ValueError(message)
 

@@ -27,6 +27,7 @@ slots, rooms, hcv, scv, feasible, penalty and final RNG states
                              [--warm-gens N] [--warm-feasible F] [--unique]
                              [--init random|greedy] [--kempe P] [--kempe-max-chain N]
                              [--slot-swap N] [--lahc N] [--lahc-history L] [--lahc-swap P]
+                             [--lahc-kempe P] [--lahc-kempe-max-chain N]
                              [--crossover uniform|guided] [--crossover-repair]
 
 --warm-gens / --warm-feasible run untimed generations first, until a fraction F
@@ -52,7 +53,10 @@ gained). Its populations part from the plain run's at the first swap applied.
 (include/ttga_lahc.h) with N steps behind every search; the record then
 carries "lahc" (N, L, P, the rows, the rows searched and improved, the
 candidates accepted and the scv gained). Its populations part from the plain
-run's at the first row that comes back better.
+run's at the first row that comes back better. With --lahc-kempe P the walk is
+tt_lahc_kempe (include/ttga_lahc_kempe.h, Island(lahc_kempe=P,
+lahc_kempe_max_chain=N)); "lahc" then also carries the share, the cap and the
+chains tried, capped, without a room and accepted and their mean length.
 --crossover guided runs Island(crossover="guided", crossover_repair=...):
 tt_ga_breed_guided (include/ttga_cx.h) breeds in place of tt_ga_breed; the
 record then carries "crossover" (the repair flag, the children, how many
@@ -206,6 +210,12 @@ def run_ga(a):
         stats = [i.lahc_stats() for i in isls]
         out["lahc"] = {"steps": a.lahc, "history": a.lahc_history, "p_swap": a.lahc_swap,
                        **{key: sum(s[key] for s in stats) for key in ("rows", "searched", "improved", "accepted", "gain")}}
+        if a.lahc_kempe > 0:
+            stats = [i.lahc_kempe_stats() for i in isls]
+            k = {key: sum(s[key] for s in stats) for key in ("tried", "capped", "no_room", "accepted", "chain_events")}
+            out["lahc"]["kempe"] = {"p_kempe": a.lahc_kempe, "max_chain": a.lahc_kempe_max_chain, "tried": k["tried"],
+                                    "capped": k["capped"], "no_room": k["no_room"], "accepted": k["accepted"],
+                                    "mean_chain": k["chain_events"] / k["accepted"] if k["accepted"] else 0.0}
     if a.crossover == "guided":
         stats = [i.cx_stats() for i in isls]
         k = {key: sum(s[key] for s in stats) for key in ("children", "crossed", "clean", "cost", "repaired")}

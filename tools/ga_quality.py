@@ -52,6 +52,13 @@ searched and improved, the candidates accepted and the scv gained. Together
 with --slot-swap M both islands run Island(slot_swap=M) and only the lahc
 differs.
 
+--lahc N --lahc-kempe P (with --lahc-swap Q, --lahc-kempe-max-chain M) compares
+the walk with Kempe-chain candidates, Island(lahc=N, lahc_swap=Q, lahc_kempe=P,
+lahc_kempe_max_chain=M) (tt_lahc_kempe, include/ttga_lahc_kempe.h), against
+Island(lahc=N) with Island's own lahc_swap, same seeds, history and
+parameters, no reference run; per run the walk's counts and the chains tried,
+capped, without a room and accepted, and their mean length.
+
 --crossover guided [--crossover-repair] does the same for the conflict-guided
 crossover: Island(crossover="guided", crossover_repair=...) (tt_ga_breed_guided,
 include/ttga_cx.h) against the island without it, same seeds and parameters, no
@@ -90,7 +97,8 @@ def summarize(final, feas, trace, checkpoints):
 
 def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch", unique=False, stats_out=None,
                 init="random", kempe=0.0, kempe_max_chain=0, slot_swap=0, lahc=0, lahc_history=500,
-                lahc_swap=0.5, crossover="uniform", crossover_repair=False):
+                lahc_swap=0.5, crossover="uniform", crossover_repair=False, lahc_kempe=0.0,
+                lahc_kempe_max_chain=0):
     import torch
 
     from ttga import native, stages
@@ -128,6 +136,8 @@ def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch", uni
             stage = next((s for s in ("cx", "lahc", "slot_swap", "kempe", "unique") if s in isl.on), None)
             if stage:        # the first of these that is on
                 stats_out.append(getattr(isl, stage + "_stats")())
+                if stage == "lahc" and "lahc_kempe" in isl.on:
+                    stats_out[-1] = dict(stats_out[-1], kempe=isl.lahc_kempe_stats())
             else:            # the plain island's distinct genomes, for the comparison
                 first = dp.genome_first(isl.pop["slot"], isl.pop["room"])
                 stats_out.append({"distinct": int((first == torch.arange(pop, dtype=torch.int32, device="cuda")).sum())})
@@ -187,7 +197,8 @@ def main():
         "slot_swap": f"N > 0: compare Island(slot_swap=N) {plain}",
         "lahc": f"N > 0: compare Island(lahc=N) {without}",
         "crossover": f"guided: compare Island(crossover='guided') {without}",
-        "lahc_history": None, "lahc_swap": None, "crossover_repair": None})
+        "lahc_kempe": f"P > 0 (with --lahc N): compare Island(lahc=N, lahc_kempe=P) with Island(lahc=N)",
+        "lahc_history": None, "lahc_swap": None, "crossover_repair": None, "lahc_kempe_max_chain": None})
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     from scipy import stats
@@ -243,6 +254,27 @@ def main():
         cap = {"kempe_max_chain": a.kempe_max_chain}
         return run(("device", "device_kempe"), (dict(cap, kempe=0.0), dict(cap, kempe=a.kempe)), "kempe_vs_plain",
                    ("median_kempe", "median_plain"), extras)
+    if a.lahc_kempe > 0:
+        message = stages.lahc_kempe_error(a.lahc, a.lahc_swap, a.lahc_kempe)
+        if message:
+            raise SystemExit(message)
+        res.update(rest, lahc_kempe=a.lahc_kempe, lahc_kempe_max_chain=a.lahc_kempe_max_chain)
+        default_swap = ap.get_default("lahc_swap")
+        res["lahc_swap_without"] = default_swap
+
+        def extras(st, with_stage):
+            out = {"lahc_stats": st}
+            if with_stage:
+                k = [s["kempe"] for s in st]
+                tried, acc = max(1, sum(x["tried"] for x in k)), sum(x["accepted"] for x in k)
+                out.update(no_room_share=sum(x["no_room"] for x in k) / tried,
+                           capped_share=sum(x["capped"] for x in k) / tried, accepted_share=acc / tried,
+                           mean_chain=sum(x["chain_events"] for x in k) / acc if acc else 0.0)
+            return out
+        return run(("device_lahc", "device_lahc_kempe"),
+                   (dict(rest, lahc_swap=default_swap),
+                    dict(rest, lahc_kempe=a.lahc_kempe, lahc_kempe_max_chain=a.lahc_kempe_max_chain)),
+                   "lahc_kempe_vs_lahc", ("median_lahc_kempe", "median_lahc"), extras, plain_stats=True)
     if a.lahc > 0:
         res.update(rest)
 
