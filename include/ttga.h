@@ -36,7 +36,8 @@
  * whole timeslots trade their events while that lowers scv), ttga_lahc.h
  * (late-acceptance hill climbing over feasible rows: single-event moves that
  * keep hcv 0, the best row seen comes back; it brings in ttga_lahc_kempe.h,
- * the same walk with Kempe chains among its candidates) and ttga_cx.h (a conflict-guided
+ * the same walk with Kempe chains among its candidates, and ttga_lahc_kempe_aug.h, which
+ * finds those chains' rooms by augmenting paths) and ttga_cx.h (a conflict-guided
  * crossover: each event takes the parent's slot that clashes less with what
  * the child holds already, and a breed call built on it).
  */

@@ -105,4 +105,8 @@ int tt_lahc(const tt_problem* p, uint8_t* slot, uint8_t* room, int64_t* rng, int
  * declared in ttga_lahc_kempe.h, which this header brings in. */
 #include "ttga_lahc_kempe.h"
 
+/* And that walk with the chains' rooms found by augmenting paths is declared
+ * in ttga_lahc_kempe_aug.h. */
+#include "ttga_lahc_kempe_aug.h"
+
 #endif /* TTGA_LAHC_H */

@@ -1,0 +1,93 @@
+// A consumer of tt_lahc_kempe_aug (include/ttga_lahc_kempe_aug.h, through ttga_lahc.h)
+// written as the reference's own code is: C++98 with the reference's flags
+// (g++ -Wall -ansi -O3). tests/test_lahc_kempe_aug_cpu.py builds it warning-free, links it
+// against libttga.so and runs it: without a GPU tt_problem_create stops at
+// TT_ERR_DEVICE and the null-handle checks run; with one, the argument checks
+// against a live handle (the device path is exercised by the GPU tests).
+#include <cstdio>
+#include <vector>
+
+#include "ttga_lahc.h"
+
+namespace {
+
+struct Instance {
+    int E, R, F, S;
+    std::vector<int32_t> roomSize, studentEvents, roomFeatures, eventFeatures;
+};
+
+Instance make_instance() {
+    Instance in;
+    in.E = 70; in.R = 3; in.F = 2; in.S = 40;
+    in.roomSize.assign(in.R, 40);
+    in.studentEvents.resize(in.S * in.E);
+    in.roomFeatures.assign(in.R * in.F, 1);
+    in.eventFeatures.assign(in.E * in.F, 0);
+    for (int s = 0; s < in.S; ++s)
+        for (int e = 0; e < in.E; ++e) in.studentEvents[s * in.E + e] = (s * 7 + e * 3) % 11 == 0;
+    return in;
+}
+
+int fail(const char* what, int rc) {
+    std::printf("%s rc=%d: %s\n", what, rc, tt_last_error());
+    return rc ? rc : 10;
+}
+
+}  // namespace
+
+int main() {
+    Instance in = make_instance();
+    int bad = 0;
+    tt_problem* tp = NULL;
+    int rc = tt_problem_create(in.E, in.R, in.F, in.S, &in.roomSize[0], &in.studentEvents[0], &in.roomFeatures[0],
+                               &in.eventFeatures[0], /*device=*/0, &tp);
+    uint8_t genes[8] = {0};
+    int64_t rng[8] = {1};
+    int32_t out[8] = {0};
+    if (rc == TT_ERR_DEVICE) {
+        std::printf("tt_problem_create TT_ERR_DEVICE: %s\n", tt_last_error());
+    bad += tt_lahc_kempe_aug(NULL, genes, genes, rng, 1, 10, 5, 0.25, 0.5, 0,
+                             1, out, out, out, out, out, out, NULL) != TT_ERR_INVALID;
+    bad += tt_lahc_kempe_aug(NULL, NULL, NULL, NULL, -1, -1, 0, 2.0, 0.5, 0,
+                             1, NULL, NULL, NULL, NULL, NULL, NULL, NULL) != TT_ERR_INVALID;
+        std::printf("null-handle checks: %d wrong\n", bad);
+        return bad ? 10 : TT_ERR_DEVICE;
+    }
+    if (rc != TT_OK) return fail("tt_problem_create", rc);
+    // bad arguments with a live handle are rejected before any launch
+    bad += tt_lahc_kempe_aug(tp, NULL, genes, rng, 1, 10, 5, 0.25, 0.5, 0,
+                             1, out, out, out, out, out, out, NULL) != TT_ERR_INVALID;
+    bad += tt_lahc_kempe_aug(tp, genes, NULL, rng, 1, 10, 5, 0.25, 0.5, 0,
+                             1, out, out, out, out, out, out, NULL) != TT_ERR_INVALID;
+    bad += tt_lahc_kempe_aug(tp, genes, genes, NULL, 1, 10, 5, 0.25, 0.5, 0,
+                             1, out, out, out, out, out, out, NULL) != TT_ERR_INVALID;
+    bad += tt_lahc_kempe_aug(tp, genes, genes, rng, -1, 10, 5, 0.25, 0.5, 0,
+                             1, out, out, out, out, out, out, NULL) != TT_ERR_INVALID;
+    bad += tt_lahc_kempe_aug(tp, genes, genes, rng, 1, -1, 5, 0.25, 0.5, 0,
+                             1, out, out, out, out, out, out, NULL) != TT_ERR_INVALID;
+    bad += tt_lahc_kempe_aug(tp, genes, genes, rng, 1, 10, 0, 0.25, 0.5, 0,
+                             1, out, out, out, out, out, out, NULL) != TT_ERR_INVALID;
+    bad += tt_lahc_kempe_aug(tp, genes, genes, rng, 1, 10, 5, 1.5, 0.5, 0,
+                             1, out, out, out, out, out, out, NULL) != TT_ERR_INVALID;
+    bad += tt_lahc_kempe_aug(tp, genes, genes, rng, 1, 10, 5, -0.5, 0.5, 0,
+                             1, out, out, out, out, out, out, NULL) != TT_ERR_INVALID;
+    bad += tt_lahc_kempe_aug(tp, genes, genes, rng, 1, 10, 5, 0.25, 1.5, 0,
+                             1, out, out, out, out, out, out, NULL) != TT_ERR_INVALID;
+    bad += tt_lahc_kempe_aug(tp, genes, genes, rng, 1, 10, 5, 0.25, -0.5, 0,
+                             1, out, out, out, out, out, out, NULL) != TT_ERR_INVALID;
+    bad += tt_lahc_kempe_aug(tp, genes, genes, rng, 1, 10, 5, 0.25, 0.5, -1,
+                             1, out, out, out, out, out, out, NULL) != TT_ERR_INVALID;
+    bad += tt_lahc_kempe_aug(tp, genes, genes, rng, 1, 10, 5, 0.75, 0.5, 0,
+                             1, out, out, out, out, out, out, NULL) != TT_ERR_INVALID;
+    bad += tt_lahc_kempe_aug(tp, genes, genes, rng, 1, 10, 5, 0.25, 0.5, 0,
+                             2, out, out, out, out, out, out, NULL) != TT_ERR_INVALID;
+    bad += tt_lahc_kempe_aug(tp, genes, genes, rng, 0, 10, 5, 0.25, 0.5, 0,
+                             -1, NULL, NULL, NULL, NULL, NULL, NULL, NULL) != TT_ERR_INVALID;
+    bad += tt_lahc_kempe_aug(tp, genes, genes, rng, 0, 10, 5, 0.25, 0.5, 0,
+                             1, NULL, NULL, NULL, NULL, NULL, NULL, NULL) != TT_OK;
+    bad += tt_lahc_kempe_aug(tp, genes, genes, rng, 0, 10, 5, 0.25, 0.5, 0,
+                             0, NULL, NULL, NULL, NULL, NULL, NULL, NULL) != TT_OK;
+    std::printf("null-buffer checks: %d wrong\n", bad);
+    tt_problem_destroy(tp);
+    return bad ? 10 : TT_OK;
+}

@@ -2,51 +2,12 @@
 //   tt_lahc_kempe  tt_lahc's walk with a third kind of candidate: the connected
 //                  component of e1 in the conflict graph of its slot and a second slot
 //                  changes sides as a whole, its rooms chosen directly
-// No counterpart in the reference; its call site is tt_lahc's.
-//
-// tt_lahc.hip's header holds for the state and for Move1 / Move2, whose code here is
-// lahc_kernel's. A chain K on a feasible row: a student of an event of K attends one
-// event of the two slots, or one on each side, both of them in K. The first kind's mask
-// flips both slots' bits, the second kind's mask stays. A slot of a feasible row holds
-// at most R <= 64 events (one room each), so a chain has at most 128.
-#include "../../include/ttga_lahc.h"
-#include "tt_internal.h"
-#include "tt_lahc_common.h"
+// No counterpart in the reference; its call site is tt_lahc's. The walk itself is
+// tt_lahc_kempe_walk.h's, which tt_lahc_kempe_aug.hip shares.
+#include "tt_lahc_kempe_walk.h"
 
 namespace ttga {
 
-constexpr int kChainMax = 2 * kMaxRooms;    // the events of two slots of a feasible row
-// correlation-row words a lane accumulates (words l, l + 64): 128 words = 8,192 events;
-// the LDS formula admits no more than 101 words (47 bitset words and 256 gene bytes a word)
-constexpr int kLkLaneWords = 2;
-// klist[128] i32 | koff[128 + 4] i32 | kroom[128] u8
-constexpr size_t kLkFixedBytes = 4 * kChainMax + 4 * (kChainMax + 4) + kChainMax;
-
-// LDS of one wave: set[45][EW64] u64 | occ[45] u64 | K[EW64] u64 | F[EW64] u64 | mask[S] u64 |
-//                  hist[L] i32 | klist | koff | sl[E] | rr[E] | bsl[E] | brr[E] | kroom  (u8)
-__host__ __device__ inline size_t lahc_kempe_lds_bytes(int E, int S, int L) {
-    return 8 * ((size_t)(kSlots + 2) * (size_t)((E + 63) / 64) + kSlots + (size_t)S) + 4 * (size_t)L + 4 * (size_t)E +
-           kLkFixedBytes;
-}
-
-// a 64-bit value every lane holds alike, as a scalar
-__device__ __forceinline__ uint64_t lahc_uniform64(uint64_t v) {
-    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
-           (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-}
-
-// One wave (workgroup) per individual; lahc_kernel's rules on who writes what hold for
-// Move1 and Move2. A Kempe candidate adds words that one lane writes and another reads:
-// K and F during the component search (a barrier after every round's reads and after
-// every round's writes, as kempe_kernel), and on an applied chain the two slots' event
-// bitsets (lane = word), the genes of the chain's events (lane = event of K) and the
-// student masks (lane = (event of K, student) pair): the barrier after every applied
-// move covers all three. klist, koff, kroom and occ are written by every lane with the
-// same value.
-// Loop bounds: `steps` steps. A Kempe step: at most |K| <= 128 rounds of the search, each
-// over the EW64 frontier words and the frontier's events; two passes over the at most
-// 128 events of K; ceil(pairs / 64) (event, student) pairs per lane, each with a binary
-// search of 7 steps in koff.
 __global__ __launch_bounds__(64) void lahc_kempe_kernel(DevProblem pb, uint8_t* __restrict__ slot,
                                                         uint8_t* __restrict__ room, int64_t* __restrict__ rng, int P,
                                                         int steps, int L, double p_swap, double p_kempe,
@@ -54,346 +15,8 @@ __global__ __launch_bounds__(64) void lahc_kempe_kernel(DevProblem pb, uint8_t* 
                                                         int32_t* __restrict__ penalty, int32_t* __restrict__ gain,
                                                         int32_t* __restrict__ accepted, int32_t* __restrict__ best_step,
                                                         int32_t* __restrict__ kstats) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const int E = pb.E, R = pb.R, S = pb.S, EW64 = pb.EW64, lane = threadIdx.x;
-    const long p = blockIdx.x;
-    if (p >= P) return;
-    uint64_t* set = (uint64_t*)lds;
-    uint64_t* occ = set + (size_t)kSlots * EW64;
-    uint64_t* K = occ + kSlots;
-    uint64_t* F = K + EW64;
-    uint64_t* mask = F + EW64;
-    int32_t* hist = (int32_t*)(mask + S);
-    int32_t* klist = hist + L;
-    int32_t* koff = klist + kChainMax;
-    uint8_t* sl = (uint8_t*)(koff + kChainMax + 4);
-    uint8_t* rr = sl + E;
-    uint8_t* bsl = rr + E;
-    uint8_t* brr = bsl + E;
-    uint8_t* kroom = brr + E;
-
-    // ---- entry: the row, validity, the bitsets and the hcv gate
-    bool bad = false;
-    for (int e = lane; e < E; e += 64) {
-        const uint8_t s = slot[p * E + e], r = room[p * E + e];
-        sl[e] = s;
-        rr[e] = r;
-        bad |= s >= kSlots || r >= R;
-    }
-    for (int i = lane; i < kSlots * EW64 + kSlots; i += 64) set[i] = 0ull;      // set and occ are adjacent
-    for (int i = lane; i < L; i += 64) hist[i] = 0;                             // costs are kept relative to scv0
-    __syncthreads();
-    const bool bad_row = wave_any(bad);
-    bool hard = false;                                  // a hard-constraint violation seen by this lane
-    if (!bad_row) {
-        for (int e = lane; e < E; e += 64) {
-            const int s = sl[e], r = rr[e];
-            atomicOr((unsigned long long*)&set[(size_t)s * EW64 + (e >> 6)], 1ull << (e & 63));
-            const unsigned long long old = atomicOr((unsigned long long*)&occ[s], 1ull << r);
-            hard |= ((old >> r) & 1ull) != 0ull;            // two events in one room of one slot
-            hard |= ((pb.poss[e] >> r) & 1ull) == 0ull;     // a room that is not possible
-        }
-        // two correlated events share a student: they are in one slot exactly if some
-        // student's events cover fewer slots than the student has events
-        for (int s = lane; s < S; s += 64) {
-            const int b = pb.stu_off[s], end = pb.stu_off[s + 1];
-            uint64_t m = 0ull;
-            for (int i = b; i < end; ++i) m |= 1ull << sl[pb.stu_ev[i]];
-            mask[s] = m;
-            hard |= __popcll(m) != end - b;
-        }
-        __syncthreads();
-    }
-    if (bad_row || wave_any(hard) || steps == 0) {
-        if (lane == 0) {
-            if (gain) gain[p] = 0;
-            if (accepted) accepted[p] = 0;
-            if (best_step) best_step[p] = 0;
-            if (bad_row) atomicOr(pb.status, kStatusLahcBadGene);
-        }
-        if (kstats && lane < 5) kstats[p * 5 + lane] = 0;
-        return;
-    }
-
-    // ---- the walk (cur and best relative to scv0)
-    int64_t st = rng[p];
-    int cur = 0, best = 0, n_acc = 0, b_step = 0;
-    int k_tried = 0, k_capped = 0, k_noroom = 0, k_acc = 0, k_events = 0;
-    bool live_is_best = true;                           // the best row is the row in sl / rr
-    int v = 0;
-    for (int k = 0; k < steps; ++k) {
-        const int e1 = min(max(lahc_uniform(pm_pick(st, E)), 0), E - 1);
-        const double u = pm_next(st), x = pm_next(st);
-        const bool kempe = p_kempe > 0.0 && lahc_uniform((int)(u >= kempe_from)) != 0;
-        const bool swap = !kempe && E >= 2 && lahc_uniform((int)(u < p_swap)) != 0;
-        const int a = lahc_uniform((int)sl[e1]);
-        if (kempe) {
-            int b = lahc_uniform((int)__dmul_rn(x, (double)(kSlots - 1)));
-            b += b >= a;
-            b = min(max(b, 0), kSlots - 1);
-            ++k_tried;
-            // ---- the component of e1 in the events of slots a and b
-            for (int w = lane; w < EW64; w += 64) {
-                const uint64_t k0 = w == (e1 >> 6) ? 1ull << (e1 & 63) : 0ull;
-                K[w] = k0;
-                F[w] = k0;
-            }
-            __syncthreads();
-            for (int round = 0; round < kChainMax; ++round) {
-                uint64_t acc[kLkLaneWords];
-#pragma unroll
-                for (int j = 0; j < kLkLaneWords; ++j) acc[j] = 0ull;
-                for (int fw = 0; fw < EW64; ++fw) {
-                    uint64_t xw = lahc_uniform64(F[fw]);        // one address for the wave
-                    for (int g = 0; g < 64 && xw; ++g) {
-                        const int f = 64 * fw + (__ffsll((unsigned long long)xw) - 1);
-                        xw &= xw - 1;
-                        const uint64_t* cr = pb.corr64 + (size_t)f * EW64;
-#pragma unroll
-                        for (int j = 0; j < kLkLaneWords; ++j)
-                            if (64 * j + lane < EW64) acc[j] |= cr[64 * j + lane];
-                    }
-                }
-                __syncthreads();                            // every lane has read the frontier
-                bool grew = false;
-#pragma unroll
-                for (int j = 0; j < kLkLaneWords; ++j) {
-                    const int w = 64 * j + lane;
-                    if (w < EW64) {
-                        const uint64_t nw = acc[j] & (set[(size_t)a * EW64 + w] | set[(size_t)b * EW64 + w]) & ~K[w];
-                        K[w] |= nw;
-                        F[w] = nw;
-                        grew |= nw != 0ull;
-                    }
-                }
-                const bool go_on = wave_any(grew);
-                __syncthreads();
-                if (!go_on) break;
-                if (max_chain > 0) {                        // a part of K above the cap: K is, too
-                    int part = 0;
-                    for (int w = lane; w < EW64; w += 64) part += __popcll(K[w]);
-                    if (wave_sum(part) > max_chain) break;
-                }
-            }
-            int cnt = 0;
-            for (int w = lane; w < EW64; w += 64) cnt += __popcll(K[w]);
-            cnt = wave_sum(cnt);
-            bool feas = cnt <= kChainMax;
-            if (max_chain > 0 && cnt > max_chain) {
-                ++k_capped;
-                feas = false;
-            }
-            // ---- the rooms: the chain leaves its own, then takes new ones in ascending order
-            uint64_t oa = occ[a], ob = occ[b];
-            oa = lahc_uniform64(oa);
-            ob = lahc_uniform64(ob);
-            int n = 0, pairs = 0;
-            if (feas) {
-                for (int w = 0; w < EW64; ++w) {
-                    uint64_t xw = lahc_uniform64(K[w]);
-                    for (int g = 0; g < 64 && xw && n < kChainMax; ++g) {
-                        const int e = 64 * w + (__ffsll((unsigned long long)xw) - 1);
-                        xw &= xw - 1;
-                        const uint64_t rbit = 1ull << lahc_uniform((int)rr[e]);
-                        if (lahc_uniform((int)sl[e]) == a) oa &= ~rbit; else ob &= ~rbit;
-                        klist[n] = e;
-                        koff[n] = pairs;
-                        pairs += pb.ev_off[e + 1] - pb.ev_off[e];
-                        ++n;
-                    }
-                }
-                koff[n] = pairs;
-                for (int i = 0; i < n; ++i) {
-                    const int e = klist[i];
-                    const bool to_b = lahc_uniform((int)sl[e]) == a;
-                    const uint64_t f = lahc_uniform64(pb.poss[e] & ~(to_b ? ob : oa));
-                    if (f == 0ull) { feas = false; break; }
-                    const int r = __ffsll((unsigned long long)f) - 1;
-                    if (to_b) ob |= 1ull << r; else oa |= 1ull << r;
-                    kroom[i] = (uint8_t)r;
-                }
-                if (!feas) ++k_noroom;
-            }
-            if (feas) {
-                const uint64_t flip = (1ull << a) | (1ull << b);
-                const int da = a / kSlotsPerDay, db = b / kSlotsPerDay;
-                int d = 0;
-                for (int i = lane; i < pairs; i += 64) {
-                    int lo = 0, hi = n - 1;                 // the event of pair i: the last koff <= i
-                    while (lo < hi) {
-                        const int mid = (lo + hi + 1) >> 1;
-                        if (koff[mid] <= i) lo = mid; else hi = mid - 1;
-                    }
-                    const uint64_t m = mask[pb.ev_stu[pb.ev_off[klist[lo]] + i - koff[lo]]];
-                    if ((m & flip) != flip) d += lahc_mask_delta(m, flip, da, db);
-                }
-                const int cand = cur + wave_sum(d);
-                if (cand <= cur || cand <= lahc_uniform(hist[v])) {
-                    if (live_is_best && cand >= cur) {      // the row is about to leave the best one
-                        for (int e = lane; e < E; e += 64) { bsl[e] = sl[e]; brr[e] = rr[e]; }
-                        live_is_best = false;
-                        __syncthreads();                    // other lanes write these genes below
-                    }
-                    for (int i = lane; i < pairs; i += 64) {
-                        int lo = 0, hi = n - 1;
-                        while (lo < hi) {
-                            const int mid = (lo + hi + 1) >> 1;
-                            if (koff[mid] <= i) lo = mid; else hi = mid - 1;
-                        }
-                        const int s = pb.ev_stu[pb.ev_off[klist[lo]] + i - koff[lo]];
-                        const uint64_t m = mask[s];
-                        if ((m & flip) != flip) mask[s] = m ^ flip;
-                    }
-                    for (int w = lane; w < EW64; w += 64) {
-                        const uint64_t kw = K[w], sa = set[(size_t)a * EW64 + w], sb = set[(size_t)b * EW64 + w];
-                        set[(size_t)a * EW64 + w] = (sa & ~kw) | (sb & kw);
-                        set[(size_t)b * EW64 + w] = (sb & ~kw) | (sa & kw);
-                    }
-                    for (int i = lane; i < n; i += 64) {
-                        const int e = klist[i];
-                        sl[e] = (uint8_t)(a + b - sl[e]);
-                        rr[e] = kroom[i];
-                    }
-                    occ[a] = oa;
-                    occ[b] = ob;
-                    cur = cand;
-                    ++n_acc;
-                    ++k_acc;
-                    k_events += n;
-                    if (cur < best) {
-                        best = cur;
-                        b_step = k + 1;
-                        live_is_best = true;
-                    }
-                    __syncthreads();                        // masks, bitsets, genes: one lane writes, another reads
-                }
-            }
-            hist[v] = cur;
-            v = v + 1 == L ? 0 : v + 1;
-            continue;
-        }
-        const int off1 = pb.ev_off[e1], n1 = pb.ev_off[e1 + 1] - off1;
-        int e2 = e1, b, r1, r2 = 0, off2 = 0, n2 = 0;
-        bool feas;
-        if (swap) {
-            e2 = lahc_uniform((int)__dmul_rn(x, (double)(E - 1)));
-            e2 += e2 >= e1;
-            e2 = min(max(e2, 0), E - 1);
-            b = lahc_uniform((int)sl[e2]);
-            off2 = pb.ev_off[e2];
-            n2 = pb.ev_off[e2 + 1] - off2;
-            bool clash = false;
-            for (int w = lane; w < EW64; w += 64) {
-                uint64_t sb = set[(size_t)b * EW64 + w], sa = set[(size_t)a * EW64 + w];
-                if (w == (e2 >> 6)) sb &= ~(1ull << (e2 & 63));
-                if (w == (e1 >> 6)) sa &= ~(1ull << (e1 & 63));
-                clash |= ((pb.corr64[(size_t)e1 * EW64 + w] & sb) | (pb.corr64[(size_t)e2 * EW64 + w] & sa)) != 0ull;
-            }
-            const uint64_t f1 = pb.poss[e1] & ~(occ[b] & ~(1ull << rr[e2]));
-            const uint64_t f2 = pb.poss[e2] & ~(occ[a] & ~(1ull << rr[e1]));
-            r1 = lahc_uniform(__ffsll((unsigned long long)f1) - 1);
-            r2 = lahc_uniform(__ffsll((unsigned long long)f2) - 1);
-            feas = a != b && r1 >= 0 && r2 >= 0 && !wave_any(clash);
-        } else {
-            b = lahc_uniform((int)__dmul_rn(x, (double)(kSlots - 1)));
-            b += b >= a;
-            b = min(max(b, 0), kSlots - 1);
-            bool clash = false;
-            for (int w = lane; w < EW64; w += 64)
-                clash |= (pb.corr64[(size_t)e1 * EW64 + w] & set[(size_t)b * EW64 + w]) != 0ull;
-            const uint64_t f1 = pb.poss[e1] & ~occ[b];
-            r1 = lahc_uniform(__ffsll((unsigned long long)f1) - 1);
-            feas = r1 >= 0 && !wave_any(clash);
-        }
-        if (feas) {
-            // the students of e1, then (Move2) of e2; one who attends both keeps the mask:
-            // the other slot's bit is set for nobody else, the candidate being feasible
-            const uint64_t flip = (1ull << a) | (1ull << b);
-            const int da = a / kSlotsPerDay, db = b / kSlotsPerDay, n = n1 + n2;
-            int d = 0;
-            for (int i = lane; i < n; i += 64) {
-                const bool first = i < n1;
-                const uint64_t m = mask[pb.ev_stu[first ? off1 + i : off2 + i - n1]];
-                if (!swap || ((m >> (first ? b : a)) & 1ull) == 0ull) d += lahc_mask_delta(m, flip, da, db);
-            }
-            const int cand = cur + wave_sum(d);
-            if (cand <= cur || cand <= lahc_uniform(hist[v])) {
-                if (live_is_best && cand >= cur) {      // the row is about to leave the best one
-                    for (int e = lane; e < E; e += 64) { bsl[e] = sl[e]; brr[e] = rr[e]; }
-                    live_is_best = false;
-                    __syncthreads();                    // every lane writes the moved genes below
-                }
-                for (int i = lane; i < n; i += 64) {
-                    const bool first = i < n1;
-                    const int s = pb.ev_stu[first ? off1 + i : off2 + i - n1];
-                    const uint64_t m = mask[s];
-                    if (!swap || ((m >> (first ? b : a)) & 1ull) == 0ull) mask[s] = m ^ flip;
-                }
-                const uint64_t bit1 = 1ull << (e1 & 63);
-                uint64_t* wa1 = &set[(size_t)a * EW64 + (e1 >> 6)];
-                uint64_t* wb1 = &set[(size_t)b * EW64 + (e1 >> 6)];
-                *wa1 &= ~bit1;
-                *wb1 |= bit1;
-                const int ro1 = rr[e1];
-                if (swap) {
-                    const uint64_t bit2 = 1ull << (e2 & 63);
-                    uint64_t* wb2 = &set[(size_t)b * EW64 + (e2 >> 6)];
-                    uint64_t* wa2 = &set[(size_t)a * EW64 + (e2 >> 6)];
-                    *wb2 &= ~bit2;
-                    *wa2 |= bit2;
-                    const int ro2 = rr[e2];
-                    occ[a] = (occ[a] & ~(1ull << ro1)) | (1ull << r2);
-                    occ[b] = (occ[b] & ~(1ull << ro2)) | (1ull << r1);
-                    sl[e2] = (uint8_t)a;
-                    rr[e2] = (uint8_t)r2;
-                } else {
-                    occ[a] &= ~(1ull << ro1);
-                    occ[b] |= 1ull << r1;
-                }
-                sl[e1] = (uint8_t)b;
-                rr[e1] = (uint8_t)r1;
-                cur = cand;
-                ++n_acc;
-                if (cur < best) {
-                    best = cur;
-                    b_step = k + 1;
-                    live_is_best = true;
-                }
-                __syncthreads();                        // the masks: written by one lane, read by another
-            }
-        }
-        hist[v] = cur;
-        v = v + 1 == L ? 0 : v + 1;
-    }
-
-    // ---- exit: the best row
-    if (b_step > 0) {
-        const uint8_t* os = live_is_best ? sl : bsl;
-        const uint8_t* orr = live_is_best ? rr : brr;
-        for (int e = lane; e < E; e += 64) {
-            slot[p * E + e] = os[e];
-            room[p * E + e] = orr[e];
-        }
-    }
-    if (lane == 0) {
-        rng[p] = st;
-        const int g = -best;
-        if (gain) gain[p] = g;
-        if (accepted) accepted[p] = n_acc;
-        if (best_step) best_step[p] = b_step;
-        if (scv) scv[p] -= g;
-        if (penalty) {
-            const int pen = penalty[p];
-            if (pen >= 0 && pen < 1000000) penalty[p] = pen - g;
-        }
-        if (kstats) {
-            kstats[p * 5 + 0] = k_tried;
-            kstats[p * 5 + 1] = k_capped;
-            kstats[p * 5 + 2] = k_noroom;
-            kstats[p * 5 + 3] = k_acc;
-            kstats[p * 5 + 4] = k_events;
-        }
-    }
+    lahc_kempe_walk<false>(pb, slot, room, rng, P, steps, L, p_swap, p_kempe, kempe_from, max_chain, 0, scv, penalty, gain,
+                           accepted, best_step, kstats);
 }
 
 }  // namespace ttga

@@ -1,0 +1,54 @@
+// Augmenting-path rooms for the Kempe candidates of the late-acceptance walk
+// (include/ttga_lahc_kempe_aug.h):
+//   tt_lahc_kempe_aug  tt_lahc_kempe with a room_rule: where a chain event finds no free
+//                      possible room, a breadth-first search over the target slot's holders
+//                      moves them along an augmenting path
+// No counterpart in the reference; its call site is tt_lahc's. The walk is
+// tt_lahc_kempe_walk.h's with kAug, a kernel of its own next to lahc_kempe_kernel.
+#include "tt_lahc_kempe_walk.h"
+
+namespace ttga {
+
+__global__ __launch_bounds__(64) void lahc_kempe_aug_kernel(DevProblem pb, uint8_t* __restrict__ slot,
+                                                            uint8_t* __restrict__ room, int64_t* __restrict__ rng,
+                                                            int P, int steps, int L, double p_swap, double p_kempe,
+                                                            double kempe_from, int max_chain, int room_rule,
+                                                            int32_t* __restrict__ scv, int32_t* __restrict__ penalty,
+                                                            int32_t* __restrict__ gain, int32_t* __restrict__ accepted,
+                                                            int32_t* __restrict__ best_step,
+                                                            int32_t* __restrict__ kstats) {
+    lahc_kempe_walk<true>(pb, slot, room, rng, P, steps, L, p_swap, p_kempe, kempe_from, max_chain, room_rule, scv,
+                          penalty, gain, accepted, best_step, kstats);
+}
+
+}  // namespace ttga
+
+using namespace ttga;
+
+extern "C" int tt_lahc_kempe_aug(const tt_problem* p, uint8_t* slot, uint8_t* room, int64_t* rng, int P, int steps,
+                                 int history, double p_swap, double p_kempe, int max_chain, int room_rule, int32_t* scv,
+                                 int32_t* penalty, int32_t* gain, int32_t* accepted, int32_t* best_step,
+                                 int32_t* kempe_stats, void* stream) {
+    int rc = check_pop_args(p, P, slot, room);
+    if (rc) return rc;
+    if (!rng) { set_error("tt_lahc_kempe_aug: null rng buffer"); return TT_ERR_INVALID; }
+    if (steps < 0) { set_error("tt_lahc_kempe_aug: negative steps"); return TT_ERR_INVALID; }
+    if (history < 1) { set_error("tt_lahc_kempe_aug: history must be at least 1"); return TT_ERR_INVALID; }
+    if (!(p_swap >= 0.0 && p_swap <= 1.0)) { set_error("tt_lahc_kempe_aug: p_swap outside [0, 1]"); return TT_ERR_INVALID; }
+    if (!(p_kempe >= 0.0 && p_kempe <= 1.0)) { set_error("tt_lahc_kempe_aug: p_kempe outside [0, 1]"); return TT_ERR_INVALID; }
+    if (max_chain < 0) { set_error("tt_lahc_kempe_aug: negative max_chain"); return TT_ERR_INVALID; }
+    if (room_rule != 0 && room_rule != 1) { set_error("tt_lahc_kempe_aug: room_rule must be 0 or 1"); return TT_ERR_INVALID; }
+    const double kempe_from = 1.0 - p_kempe;
+    if (!(p_swap <= kempe_from)) { set_error("tt_lahc_kempe_aug: p_swap above 1 - p_kempe"); return TT_ERR_INVALID; }
+    if (P == 0) return TT_OK;
+    const size_t lds = lahc_kempe_aug_lds_bytes(p->E, p->S, history);
+    if (lds > kLahcMaxLds || p->dev.EW64 > 64 * kLkLaneWords) {
+        set_error("instance or history too large for the late-acceptance search with augmenting Kempe chains");
+        return TT_ERR_LIMIT;
+    }
+    if ((rc = use_device(p))) return rc;
+    hipLaunchKernelGGL(lahc_kempe_aug_kernel, dim3(P), dim3(64), lds, (hipStream_t)stream, p->dev, slot, room, rng, P,
+                       steps, history, p_swap, p_kempe, kempe_from, max_chain, room_rule, scv, penalty, gain, accepted,
+                       best_step, kempe_stats);
+    return check_hip(hipGetLastError(), "lahc_kempe_aug launch");
+}

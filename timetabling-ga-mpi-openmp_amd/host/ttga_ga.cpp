@@ -13,7 +13,7 @@
 //           [-p1 x -p2 y -p3 z] [--gpus G] [--islands K] [--pop N] [--generations n] [--rccl] [--stagger]
 //           [--report] [--unique] [--init random|greedy] [--kempe P] [--kempe-max-chain N]
 //           [--slot-swap N] [--lahc N] [--lahc-history L] [--lahc-swap P]
-//           [--lahc-kempe P] [--lahc-kempe-max-chain N]
+//           [--lahc-kempe P] [--lahc-kempe-max-chain N] [--lahc-kempe-rooms direct|augment]
 //           [--crossover uniform|guided] [--crossover-repair]
 //
 // --crossover guided: every sub-batch is bred by tt_ga_breed_guided
@@ -40,6 +40,12 @@
 // default: no cap). Each island then prints one {"lahcKempe": {"accepted",
 // "capped", "meanChain", "noRoom", "tried"}} line after its lahc line
 // (ttga.islands prints the same). The default is 0: tt_lahc as before.
+//
+// --lahc-kempe-rooms augment (needs --lahc-kempe P > 0): the walk is
+// tt_lahc_kempe_aug (include/ttga_lahc_kempe_aug.h) with room_rule 1 in place of
+// tt_lahc_kempe: a chain event with no free possible room moves the target
+// slot's holders along an augmenting path. The lahcKempe line then also carries
+// "rescued" and "displaced". The default is direct: no new call.
 //
 // --slot-swap N: tt_slot_swap (include/ttga_slotswap.h) with max_passes N runs
 // directly behind every tt_local_search_eval, on the same stream, and lowers
@@ -157,6 +163,7 @@ struct Stages {
     double lahc_swap = 0.5;                       // --lahc-swap
     double lahc_kempe = 0.0;                      // --lahc-kempe: tt_lahc_kempe's share of chains (0: tt_lahc)
     int lahc_kempe_max_chain = 0;                 // --lahc-kempe-max-chain (0: no cap)
+    bool lahc_kempe_augment = false;              // --lahc-kempe-rooms augment: tt_lahc_kempe_aug, room_rule 1
     bool guided = false;                          // --crossover guided: tt_ga_breed_guided breeds
     bool cx_repair = false;                       // --crossover-repair
 };
@@ -250,12 +257,15 @@ Control parse_control(int argc, char** argv) {
     take_prob(args, "--lahc-kempe", "--lahc-kempe must be a probability in [0, 1]", s.lahc_kempe);
     take_int(args, "--lahc-kempe-max-chain", 0, "--lahc-kempe-max-chain must be a non-negative integer",
              s.lahc_kempe_max_chain);
+    take_choice(args, "--lahc-kempe-rooms", "direct", "augment", "--lahc-kempe-rooms must be direct or augment",
+                s.lahc_kempe_augment);
     s.cx_repair = take_flag(args, "--crossover-repair");
     take_choice(args, "--crossover", "uniform", "guided", "--crossover must be uniform or guided", s.guided);
     if (s.cx_repair && !s.guided) bad_flag("--crossover-repair needs --crossover guided");
     if (s.lahc_kempe > 0 && s.lahc <= 0) bad_flag("--lahc-kempe needs --lahc");
     if (s.lahc_kempe > 0 && !(s.lahc_swap <= 1.0 - s.lahc_kempe))         // tt_lahc_kempe's own test
         bad_flag("--lahc-swap and --lahc-kempe must not add up to more than 1");
+    if (s.lahc_kempe_augment && !(s.lahc_kempe > 0)) bad_flag("--lahc-kempe-rooms augment needs --lahc-kempe");
     for (const char* k : {"--gpus", "--islands", "--pop", "--generations", "--children", "--stagger-parts"}) {
         auto it = std::find(args.begin(), args.end(), k);
         if (it != args.end()) {
@@ -685,7 +695,10 @@ struct Island {
     RunLog<1> chain_log;                              // --kempe: every child's chain length
     RunLog<2> swap_log;                               // --slot-swap: every searched row's gain and passes
     RunLog<2> lahc_log;                               // --lahc: every searched row's gain, accepted and feasible flag
-    RunLog<5> lk_log;                                 // --lahc-kempe: every searched row's five counts, row-major
+    // --lahc-kempe: every searched row's lk_width() counts, row-major (five; seven under
+    // --lahc-kempe-rooms augment)
+    RunLog<7> lk_log;
+    int lk_width() const { return stage.lahc_kempe_augment ? 7 : 5; }
     RunLog<2> cx_log;                                 // --crossover guided: every child's cost, repaired and flags
     int32_t* ev_order = nullptr;                      // event_order()'s, once computed
 
@@ -910,7 +923,13 @@ struct Island {
     // search, evaluation and timeslot swap; their scv and penalty are lowered in place
     void late_acceptance(const Pop& r, int64_t* g, hipStream_t s) {
         const long at = lahc_log.reserve(r.n);
-        if (stage.lahc_kempe > 0) {
+        if (stage.lahc_kempe > 0 && stage.lahc_kempe_augment) {
+            lk_log.reserve(r.n);                      // row for row with lahc_log
+            check_tt(tt_lahc_kempe_aug(tp, r.slot, r.room, g, r.n, stage.lahc, stage.lahc_history, stage.lahc_swap,
+                                       stage.lahc_kempe, stage.lahc_kempe_max_chain, 1, r.scv, r.penalty,
+                                       lahc_log.col(0) + at, lahc_log.col(1) + at, nullptr, lk_log.data + 7 * at, s),
+                     "tt_lahc_kempe_aug");
+        } else if (stage.lahc_kempe > 0) {
             lk_log.reserve(r.n);                      // row for row with lahc_log
             check_tt(tt_lahc_kempe(tp, r.slot, r.room, g, r.n, stage.lahc, stage.lahc_history, stage.lahc_swap,
                                    stage.lahc_kempe, stage.lahc_kempe_max_chain, r.scv, r.penalty, lahc_log.col(0) + at,
@@ -948,16 +967,21 @@ struct Island {
     Json lahc_kempe_report() {
         flush();
         finish();
-        std::vector<int32_t> h(5 * (size_t)lk_log.used);
+        const int width = lk_width();
+        std::vector<int32_t> h((size_t)width * (size_t)lk_log.used);
         if (lk_log.used) check_hip(hipMemcpy(h.data(), lk_log.data, 4 * h.size(), hipMemcpyDeviceToHost), "hipMemcpy");
-        long sum[5] = {0, 0, 0, 0, 0};
-        for (size_t i = 0; i < h.size(); i++) sum[i % 5] += h[i];
+        long sum[7] = {0, 0, 0, 0, 0, 0, 0};
+        for (size_t i = 0; i < h.size(); i++) sum[i % width] += h[i];
         Json k;
         k.obj["tried"] = Json::I(sum[0]);
         k.obj["capped"] = Json::I(sum[1]);
         k.obj["noRoom"] = Json::I(sum[2]);
         k.obj["accepted"] = Json::I(sum[3]);
         k.obj["meanChain"] = Json::D(sum[3] ? (double)sum[4] / (double)sum[3] : 0.0);
+        if (stage.lahc_kempe_augment) {
+            k.obj["rescued"] = Json::I(sum[5]);
+            k.obj["displaced"] = Json::I(sum[6]);
+        }
         return wrap("lahcKempe", k);
     }
 

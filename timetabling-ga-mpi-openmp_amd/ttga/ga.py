@@ -194,7 +194,8 @@ class Tally:
 
     def __init__(self, n: int, outputs, sums, dev, register: list):
         import torch
-        self.out = {k: torch.zeros((n, 5) if k == "stats" else n, dtype=torch.int32, device=dev) for k in outputs}
+        self.out = {k: torch.zeros((n, len(sums)) if k == "stats" else n, dtype=torch.int32, device=dev)
+                    for k in outputs}
         self.sums = torch.zeros(len(sums), dtype=torch.int64, device=dev)
         self.rows = 0
         register += [*self.out.values(), self.sums]
@@ -277,6 +278,12 @@ class Island(Members):
     kinds of move; lahc_kempe_stats() reports the chains. lahc_kempe=0 calls
     tt_lahc exactly as before.
 
+    lahc_kempe_rooms="augment" (needs lahc_kempe > 0): the walk is
+    tt_lahc_kempe_aug (include/ttga_lahc_kempe_aug.h) with room_rule 1 in place
+    of tt_lahc_kempe: a chain event with no free possible room moves the target
+    slot's holders along an augmenting path. lahc_kempe_stats() then also has
+    `rescued` and `displaced`. "direct" calls what the island called before.
+
     crossover="guided": every sub-batch is bred with tt_ga_breed_guided
     (include/ttga_cx.h) in place of tt_ga_breed, on the same stream and at the
     same place in the operation chain, in the handle's greedy_order(); with
@@ -295,7 +302,7 @@ class Island(Members):
                  kempe: float = 0.0, kempe_max_chain: int = 0, slot_swap: int = 0,
                  lahc: int = 0, lahc_history: int = 500, lahc_swap: float = 0.5,
                  crossover: str = "uniform", crossover_repair: bool = False,
-                 lahc_kempe: float = 0.0, lahc_kempe_max_chain: int = 0):
+                 lahc_kempe: float = 0.0, lahc_kempe_max_chain: int = 0, lahc_kempe_rooms: str = "direct"):
         """stream: a torch.cuda.Stream of the island's own, or None (torch's current
         stream). Islands multiplexed on one GPU (ttga.islands --islands K) each take
         one, so one island's launches fill the SIMD slots another's local-search tail
@@ -303,7 +310,7 @@ class Island(Members):
         synchronises its stream first, and a caller that moves data between islands
         (migration) synchronises the device around it."""
         validate(init, kempe, kempe_max_chain, slot_swap, lahc, lahc_history, lahc_swap, crossover, crossover_repair,
-                 lahc_kempe, lahc_kempe_max_chain)
+                 lahc_kempe, lahc_kempe_max_chain, lahc_kempe_rooms)
         import torch
         if not (1 <= children <= pop_size):
             raise ValueError("need 1 <= children <= pop_size")
@@ -330,6 +337,7 @@ class Island(Members):
         self.slot_swap = int(slot_swap)
         self.lahc, self.lahc_history, self.lahc_swap = int(lahc), int(lahc_history), float(lahc_swap)
         self.lahc_kempe, self.lahc_kempe_max_chain = float(lahc_kempe), int(lahc_kempe_max_chain)
+        self.lahc_kempe_rooms = lahc_kempe_rooms
         self.crossover, self.crossover_repair = crossover, bool(crossover_repair)
         self.generation = 0
         self.schedule = schedule
@@ -373,8 +381,9 @@ class Island(Members):
                                            ("lahc_kempe", self.lahc_kempe > 0),
                                            ("cx", self.crossover == "guided")) if on}
         self._init_tally = {}
-        for stage, (_, _, outputs, sums, in_init) in _TALLIED.items():
+        for stage, (_, _, outputs, _, in_init) in _TALLIED.items():
             if stage in self.on:
+                sums = self._sum_names(stage)
                 if in_init:
                     self._init_tally[stage] = Tally(self.N, outputs, sums, dev, self._extra)
                 for p in self._parts:
@@ -584,14 +593,22 @@ class Island(Members):
         t.add(int(rows["slot"].shape[0]), (passes > 0).sum(), passes.sum(), gain.sum())
 
     def _lahc(self, rows, rng, tally):
-        """tt_lahc, or with lahc_kempe > 0 tt_lahc_kempe, on the searched rows
+        """tt_lahc, or with lahc_kempe > 0 tt_lahc_kempe (tt_lahc_kempe_aug
+        under lahc_kempe_rooms="augment"), on the searched rows
         (on the current stream, behind their search and evaluation) and its
         counts, summed on the device behind the call. The rows that walk are
         the feasible ones: the call's own gate is tt_eval's hcv."""
         t = tally["lahc"]
         gain, accepted = t.out["gain"], t.out["accepted"]
         n = int(rows["slot"].shape[0])
-        if self.lahc_kempe > 0:
+        if self.lahc_kempe > 0 and self.lahc_kempe_rooms == "augment":
+            tk = tally["lahc_kempe"]
+            self.dp.lahc_kempe_aug(rows["slot"], rows["room"], rng, self.lahc, self.lahc_history, self.lahc_swap,
+                                   self.lahc_kempe, self.lahc_kempe_max_chain, 1, scv=rows["scv"],
+                                   penalty=rows["penalty"], gain=gain, accepted=accepted, best_step=t.out["best_step"],
+                                   kempe_stats=tk.out["stats"])
+            tk.add(n, *tk.out["stats"].sum(dim=0).unbind())
+        elif self.lahc_kempe > 0:
             tk = tally["lahc_kempe"]
             self.dp.lahc_kempe(rows["slot"], rows["room"], rng, self.lahc, self.lahc_history, self.lahc_swap,
                                self.lahc_kempe, self.lahc_kempe_max_chain, scv=rows["scv"], penalty=rows["penalty"],
@@ -603,10 +620,19 @@ class Island(Members):
                          best_step=t.out["best_step"])
         t.add(n, (rows["feasible"] != 0).sum(), (gain > 0).sum(), accepted.sum(), gain.sum())
 
+    def _sum_names(self, stage: str) -> tuple:
+        """The names of a tallied stage's sums: _TALLIED's, and for the chains
+        of the walk under lahc_kempe_rooms="augment" tt_lahc_kempe_aug's two more."""
+        names = _TALLIED[stage][3]
+        if stage == "lahc_kempe" and self.lahc_kempe_rooms == "augment":
+            names += ("rescued", "displaced")
+        return names
+
     def _stats(self, stage: str) -> dict:
         """A tallied stage's row count and sums over all its holders, as Python
         ints. Pending sub-batches are replaced first; synchronises."""
-        need, count, _, names, _ = _TALLIED[stage]
+        need, count, _, _, _ = _TALLIED[stage]
+        names = self._sum_names(stage)
         if stage not in self.on:
             raise ValueError(f"{stage}_stats() needs Island({need})")
         self.flush()
@@ -630,7 +656,9 @@ class Island(Members):
     def lahc_kempe_stats(self) -> dict:
         """Island(lahc_kempe > 0): the rows tt_lahc_kempe was called on, and of
         their Kempe candidates those tried, capped, without a room and
-        accepted, and the events of the accepted chains."""
+        accepted, and the events of the accepted chains; under
+        lahc_kempe_rooms="augment" also the candidates a path `rescued` and the
+        bystanders the accepted chains `displaced`."""
         return self._stats("lahc_kempe")
 
     def slot_swap_stats(self) -> dict:
@@ -852,11 +880,14 @@ def lahc_line(stats: dict) -> str:
 
 def lahc_kempe_line(stats: dict) -> str:
     """The drivers' --lahc-kempe line of one island: Island.lahc_kempe_stats()
-    with the mean length of the accepted chains (0 when there are none)."""
+    with the mean length of the accepted chains (0 when there are none), and
+    under --lahc-kempe-rooms augment `rescued` and `displaced` as well."""
     accepted = int(stats["accepted"])
-    return json_line({"lahcKempe": {"tried": int(stats["tried"]), "capped": int(stats["capped"]),
-                                    "noRoom": int(stats["no_room"]), "accepted": accepted,
-                                    "meanChain": float(stats["chain_events"]) / accepted if accepted else 0.0}})
+    line = {"tried": int(stats["tried"]), "capped": int(stats["capped"]), "noRoom": int(stats["no_room"]),
+            "accepted": accepted, "meanChain": float(stats["chain_events"]) / accepted if accepted else 0.0}
+    if "rescued" in stats:
+        line.update(rescued=int(stats["rescued"]), displaced=int(stats["displaced"]))
+    return json_line({"lahcKempe": line})
 
 
 def crossover_line(stats: dict) -> str:

@@ -44,6 +44,11 @@ Reference correspondence:
   ttga.ga.Island(lahc_kempe=P, lahc_kempe_max_chain=N); each island then prints
   a `lahcKempe` line after the lahc line: chains tried, capped, without a
   room, accepted, mean length of the accepted; 0: tt_lahc as before),
+  `--lahc-kempe-rooms direct|augment` (with --lahc-kempe P > 0; augment: the
+  walk is tt_lahc_kempe_aug, include/ttga_lahc_kempe_aug.h, which finds a
+  chain's rooms by augmenting paths, ttga.ga.Island(lahc_kempe_rooms="augment");
+  the lahcKempe line then also carries the chains a path rescued and the
+  bystanders displaced; the default is direct, which issues no new call),
   `--crossover uniform|guided` / `--crossover-repair` (guided: the children are
   bred by tt_ga_breed_guided, include/ttga_cx.h, ttga.ga.Island(crossover=
   "guided", crossover_repair=...); each island then prints a `crossover` line
@@ -118,6 +123,9 @@ def parse_control(argv, out=sys.stdout, err=sys.stderr) -> dict:
         if message:
             err.write(f"Error: {message}\n")
             raise SystemExit(1)
+    if extra.get("lahc_kempe_rooms") == "augment" and not extra.get("lahc_kempe", 0) > 0:
+        err.write(f"Error: {stages.LAHC_KEMPE_ROOMS_NEEDS_KEMPE}\n")
+        raise SystemExit(1)
     if len(args) % 2 != 0:
         err.write("Parse error: Number of command line parameters incorrect\nUsage:\n" + USAGE + "\n")
         raise SystemExit(1)

@@ -49,6 +49,10 @@ LAHC_EXPORTS = ("tt_lahc",)
 # include/ttga_lahc_kempe.h (brought in by ttga_lahc.h)
 LAHC_KEMPE_EXPORTS = ("tt_lahc_kempe",)
 
+# include/ttga_lahc_kempe_aug.h (brought in by ttga_lahc.h)
+LAHC_KEMPE_AUG_EXPORTS = ("tt_lahc_kempe_aug",)
+ROOM_RULES = ("direct", "augment")          # tt_lahc_kempe_aug's room_rule 0 and 1
+
 # include/ttga_cx.h
 CX_EXPORTS = ("tt_crossover_guided", "tt_ga_breed_guided")
 
@@ -125,6 +129,8 @@ def load(path: os.PathLike | str | None = None) -> ctypes.CDLL:
     lib.tt_lahc.restype = ctypes.c_int
     lib.tt_lahc_kempe.argtypes = [vp, vp, vp, vp, i32, i32, i32, dbl, dbl, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.tt_lahc_kempe.restype = ctypes.c_int
+    lib.tt_lahc_kempe_aug.argtypes = [vp, vp, vp, vp, i32, i32, i32, dbl, dbl, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.tt_lahc_kempe_aug.restype = ctypes.c_int
     lib.tt_crossover_guided.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]
     lib.tt_crossover_guided.restype = ctypes.c_int
     lib.tt_ga_breed_guided.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, dbl, dbl, i32, i32, vp, vp, vp, vp, vp, vp]
@@ -537,6 +543,30 @@ class DeviceProblem:
                                                 int(steps), int(history), float(p_swap), float(p_kempe), int(max_chain),
                                                 ptr(scv), ptr(penalty), ptr(gain), ptr(accepted), ptr(best_step),
                                                 ptr(kempe_stats), self._stream(slot)))
+
+    def lahc_kempe_aug(self, slot, room, rng, steps, history, p_swap=0.25, p_kempe=0.5, max_chain=0, room_rule=1,
+                       scv=None, penalty=None, gain=None, accepted=None, best_step=None, kempe_stats=None):
+        """tt_lahc_kempe_aug in place on slot, room [P, E] and rng [P]:
+        lahc_kempe() with a room_rule (0: its direct rule; 1: a chain event with
+        no free possible room moves the target slot's holders along an
+        augmenting path). The optional tensors are lahc_kempe()'s, with
+        kempe_stats int32 [P, 7]: its five counts, the chains a path rescued
+        and the bystanders the accepted chains displaced."""
+        import torch
+        P = self._pop(slot, room)
+        self._rng(rng, P)
+        for name, t, n in (("scv", scv, P), ("penalty", penalty, P), ("gain", gain, P), ("accepted", accepted, P),
+                           ("best_step", best_step, P), ("kempe_stats", kempe_stats, 7 * P)):
+            if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n
+                                      and t.device == slot.device):
+                raise ValueError(f"{name} must be a contiguous int32 CUDA tensor of {'7 P' if n != P else 'P'} entries "
+                                 "on the population's device")
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)    # noqa: E731
+        _check(self.lib, self.lib.tt_lahc_kempe_aug(self.handle, slot.data_ptr(), room.data_ptr(), rng.data_ptr(), P,
+                                                    int(steps), int(history), float(p_swap), float(p_kempe),
+                                                    int(max_chain), int(room_rule), ptr(scv), ptr(penalty), ptr(gain),
+                                                    ptr(accepted), ptr(best_step), ptr(kempe_stats),
+                                                    self._stream(slot)))
 
     # -- conflict-guided crossover (include/ttga_cx.h) -------------------------------
     def _cx_args(self, slot, order, P, cost, repaired):

@@ -35,6 +35,10 @@ FLAGS = (
          "0: tt_lahc"),
     Flag("--lahc-kempe-max-chain", "lahc_kempe_max_chain", "int", (0, INT_MAX),
          "--lahc-kempe-max-chain must be a non-negative integer", "the cap on a chain's length in the walk (0: none)"),
+    Flag("--lahc-kempe-rooms", "lahc_kempe_rooms", "choice", ("direct", "augment"),
+         "--lahc-kempe-rooms must be direct or augment",
+         "the room rule of the walk's chains: tt_lahc_kempe's direct one, or augmenting paths, tt_lahc_kempe_aug "
+         "(Island(lahc_kempe_rooms=...))"),
     Flag("--crossover-repair", "crossover_repair", "flag", None, None,
          "guided: an event that clashes in both parents' slots goes to a slot of least cost"),
     Flag("--crossover", "crossover", "choice", ("uniform", "guided"), "--crossover must be uniform or guided",
@@ -48,6 +52,10 @@ LAHC_KEMPE_NEEDS_LAHC = "--lahc-kempe needs --lahc"
 LAHC_KEMPE_SHARES = "--lahc-swap and --lahc-kempe must not add up to more than 1"
 
 
+# and where --lahc-kempe-rooms augment comes without chains
+LAHC_KEMPE_ROOMS_NEEDS_KEMPE = "--lahc-kempe-rooms augment needs --lahc-kempe"
+
+
 def lahc_kempe_error(lahc, lahc_swap, lahc_kempe):
     """The message for a --lahc-kempe that does not go with --lahc and
     --lahc-swap (the values in force, defaults included), or None."""
@@ -59,7 +67,7 @@ def lahc_kempe_error(lahc, lahc_swap, lahc_kempe):
 
 
 def validate(init, kempe, kempe_max_chain, slot_swap, lahc, lahc_history, lahc_swap, crossover, crossover_repair,
-             lahc_kempe=0.0, lahc_kempe_max_chain=0):
+             lahc_kempe=0.0, lahc_kempe_max_chain=0, lahc_kempe_rooms="direct"):
     """Island's stage arguments: the first one out of range raises ValueError."""
     for ok, message in (
             (crossover in ("uniform", "guided"), "crossover must be 'uniform' or 'guided'"),
@@ -75,7 +83,9 @@ def validate(init, kempe, kempe_max_chain, slot_swap, lahc, lahc_history, lahc_s
             (int(lahc_kempe_max_chain) >= 0, "lahc_kempe_max_chain must be >= 0 (0: no cap)"),
             (not float(lahc_kempe) > 0 or int(lahc) > 0, "lahc_kempe > 0 needs lahc > 0"),
             (not float(lahc_kempe) > 0 or float(lahc_swap) <= 1.0 - float(lahc_kempe),
-             "lahc_swap + lahc_kempe must be <= 1")):
+             "lahc_swap + lahc_kempe must be <= 1"),
+            (lahc_kempe_rooms in ("direct", "augment"), "lahc_kempe_rooms must be 'direct' or 'augment'"),
+            (lahc_kempe_rooms != "augment" or float(lahc_kempe) > 0, "lahc_kempe_rooms='augment' needs lahc_kempe > 0")):
         if not ok:
             raise ValueError(message)
 

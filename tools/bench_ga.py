@@ -56,7 +56,9 @@ candidates accepted and the scv gained). Its populations part from the plain
 run's at the first row that comes back better. With --lahc-kempe P the walk is
 tt_lahc_kempe (include/ttga_lahc_kempe.h, Island(lahc_kempe=P,
 lahc_kempe_max_chain=N)); "lahc" then also carries the share, the cap and the
-chains tried, capped, without a room and accepted and their mean length.
+chains tried, capped, without a room and accepted and their mean length; with
+--lahc-kempe-rooms augment (tt_lahc_kempe_aug, include/ttga_lahc_kempe_aug.h)
+also the rule, the chains a path rescued and the bystanders displaced.
 --crossover guided runs Island(crossover="guided", crossover_repair=...):
 tt_ga_breed_guided (include/ttga_cx.h) breeds in place of tt_ga_breed; the
 record then carries "crossover" (the repair flag, the children, how many
@@ -216,6 +218,9 @@ def run_ga(a):
             out["lahc"]["kempe"] = {"p_kempe": a.lahc_kempe, "max_chain": a.lahc_kempe_max_chain, "tried": k["tried"],
                                     "capped": k["capped"], "no_room": k["no_room"], "accepted": k["accepted"],
                                     "mean_chain": k["chain_events"] / k["accepted"] if k["accepted"] else 0.0}
+            if a.lahc_kempe_rooms == "augment":       # tt_lahc_kempe_aug's two more counts
+                out["lahc"]["kempe"].update(rooms="augment", rescued=sum(s["rescued"] for s in stats),
+                                            displaced=sum(s["displaced"] for s in stats))
     if a.crossover == "guided":
         stats = [i.cx_stats() for i in isls]
         k = {key: sum(s[key] for s in stats) for key in ("children", "crossed", "clean", "cost", "repaired")}

@@ -59,6 +59,13 @@ Island(lahc=N) with Island's own lahc_swap, same seeds, history and
 parameters, no reference run; per run the walk's counts and the chains tried,
 capped, without a room and accepted, and their mean length.
 
+--lahc N --lahc-kempe P --lahc-kempe-rooms augment compares the room rules of
+those chains: Island(lahc_kempe_rooms="augment") (tt_lahc_kempe_aug,
+include/ttga_lahc_kempe_aug.h: rooms by augmenting paths) against the same
+island with the direct rule, same seeds, flags and parameters, no reference
+run; per run the walk's counts and the chains' (with the rule also those a
+path rescued and the bystanders displaced).
+
 --crossover guided [--crossover-repair] does the same for the conflict-guided
 crossover: Island(crossover="guided", crossover_repair=...) (tt_ga_breed_guided,
 include/ttga_cx.h) against the island without it, same seeds and parameters, no
@@ -98,7 +105,7 @@ def summarize(final, feas, trace, checkpoints):
 def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch", unique=False, stats_out=None,
                 init="random", kempe=0.0, kempe_max_chain=0, slot_swap=0, lahc=0, lahc_history=500,
                 lahc_swap=0.5, crossover="uniform", crossover_repair=False, lahc_kempe=0.0,
-                lahc_kempe_max_chain=0):
+                lahc_kempe_max_chain=0, lahc_kempe_rooms="direct"):
     import torch
 
     from ttga import native, stages
@@ -198,6 +205,7 @@ def main():
         "lahc": f"N > 0: compare Island(lahc=N) {without}",
         "crossover": f"guided: compare Island(crossover='guided') {without}",
         "lahc_kempe": f"P > 0 (with --lahc N): compare Island(lahc=N, lahc_kempe=P) with Island(lahc=N)",
+        "lahc_kempe_rooms": "augment (with --lahc N --lahc-kempe P): compare the room rules, same flags otherwise",
         "lahc_history": None, "lahc_swap": None, "crossover_repair": None, "lahc_kempe_max_chain": None})
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -254,6 +262,8 @@ def main():
         cap = {"kempe_max_chain": a.kempe_max_chain}
         return run(("device", "device_kempe"), (dict(cap, kempe=0.0), dict(cap, kempe=a.kempe)), "kempe_vs_plain",
                    ("median_kempe", "median_plain"), extras)
+    if a.lahc_kempe_rooms == "augment" and not a.lahc_kempe > 0:
+        raise SystemExit(stages.LAHC_KEMPE_ROOMS_NEEDS_KEMPE)
     if a.lahc_kempe > 0:
         message = stages.lahc_kempe_error(a.lahc, a.lahc_swap, a.lahc_kempe)
         if message:
@@ -270,7 +280,16 @@ def main():
                 out.update(no_room_share=sum(x["no_room"] for x in k) / tried,
                            capped_share=sum(x["capped"] for x in k) / tried, accepted_share=acc / tried,
                            mean_chain=sum(x["chain_events"] for x in k) / acc if acc else 0.0)
+                if "rescued" in k[0]:
+                    out.update(rescued_share=sum(x["rescued"] for x in k) / tried,
+                               displaced_per_accepted=sum(x["displaced"] for x in k) / acc if acc else 0.0)
             return out
+        if a.lahc_kempe_rooms == "augment":          # the two room rules, everything else alike
+            res["lahc_kempe_rooms"] = a.lahc_kempe_rooms
+            chains = dict(rest, lahc_kempe=a.lahc_kempe, lahc_kempe_max_chain=a.lahc_kempe_max_chain)
+            return run(("device_direct", "device_augment"), (chains, dict(chains, lahc_kempe_rooms="augment")),
+                       "augment_vs_direct", ("median_augment", "median_direct"),
+                       lambda st, _: extras(st, True), plain_stats=True)
         return run(("device_lahc", "device_lahc_kempe"),
                    (dict(rest, lahc_swap=default_swap),
                     dict(rest, lahc_kempe=a.lahc_kempe, lahc_kempe_max_chain=a.lahc_kempe_max_chain)),
