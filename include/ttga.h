@@ -37,7 +37,8 @@
  * (late-acceptance hill climbing over feasible rows: single-event moves that
  * keep hcv 0, the best row seen comes back; it brings in ttga_lahc_kempe.h,
  * the same walk with Kempe chains among its candidates, and ttga_lahc_kempe_aug.h, which
- * finds those chains' rooms by augmenting paths) and ttga_cx.h (a conflict-guided
+ * finds those chains' rooms by augmenting paths, and ttga_lahc_multi.h, which runs
+ * several such walks from every row and keeps the best) and ttga_cx.h (a conflict-guided
  * crossover: each event takes the parent's slot that clashes less with what
  * the child holds already, and a breed call built on it).
  */

@@ -109,4 +109,8 @@ int tt_lahc(const tt_problem* p, uint8_t* slot, uint8_t* room, int64_t* rng, int
  * in ttga_lahc_kempe_aug.h. */
 #include "ttga_lahc_kempe_aug.h"
 
+/* And K such walks from every row at once, the best of them kept, are declared
+ * in ttga_lahc_multi.h. */
+#include "ttga_lahc_multi.h"
+
 #endif /* TTGA_LAHC_H */

@@ -39,6 +39,37 @@ __host__ __device__ inline size_t lahc_kempe_aug_lds_bytes(int E, int S, int L) 
     return lahc_kempe_lds_bytes(E, S, L) + kLkAugBytes;
 }
 
+// tt_lahc_multi's work buffer for P rows of K walkers, wave q = row * K + walker:
+//   state[P] i64      the row's stream state behind all K walks (the last walker writes it)
+//   nums[P K][12] i32 walker q's gain, accepted, best_step, the seven counts, walked (0: the
+//                     row is closed or steps is 0: nothing else of q is written), a pad
+//   rows[P K][2][E] u8 walker q's exit slot and room genes, written only if best_step > 0
+constexpr int kLmNums = 12, kLmGain = 0, kLmAccepted = 1, kLmBestStep = 2, kLmStats = 3, kLmWalked = 10;
+struct LahcMultiWork {
+    int64_t* state;
+    int32_t* nums;
+    uint8_t* rows;
+};
+__host__ __device__ inline LahcMultiWork lahc_multi_work(void* work, long P, long K, int E) {
+    uint8_t* w = (uint8_t*)work;
+    return {(int64_t*)w, (int32_t*)(w + 8 * (size_t)P), w + 8 * (size_t)P + 4 * (size_t)kLmNums * (size_t)(P * K)};
+}
+__host__ __device__ inline size_t lahc_multi_work_size(long P, long K, int E) {
+    return 8 * (size_t)P + (4 * (size_t)kLmNums + 2 * (size_t)E) * (size_t)(P * K);
+}
+
+// Walker w's stream state: s after 3 * steps * w draws. The product form of pm_mulmod holds
+// for a state below 2^31 - 1 only, and rng[] may hold any 64-bit seed: draws are taken with
+// pm_next until the state is in range (at least one; a 64-bit state shrinks by a factor of
+// 45 a draw, so a dozen at the most), the rest is one jump. 16807 has an order that divides
+// 2^31 - 2, so the exponent is reduced by it.
+__device__ __forceinline__ int64_t lahc_multi_start(int64_t s, int steps, int w) {
+    int64_t n = 3ll * steps * w;
+    for (int g = 0; g < 64 && n > 0 && (g == 0 || (uint64_t)s >= (uint64_t)kPmM); ++g, --n) pm_next(s);
+    if (n > 0 && (uint64_t)s < (uint64_t)kPmM) s = pm_mulmod((uint32_t)s, pm_pow((int)(n % (int64_t)(kPmM - 1))));
+    return s;
+}
+
 // a 64-bit value every lane holds alike, as a scalar
 __device__ __forceinline__ uint64_t lahc_uniform64(uint64_t v) {
     return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
@@ -76,17 +107,26 @@ __device__ __forceinline__ uint64_t lahc_lane64(uint64_t v, int r) {
 // Loop bounds: one search queues every room at most once (V), so it pops at most R <= 64
 // rooms and queues at most 64; a path has at most 64 rooms; a chain runs at most 128
 // searches.
-template <bool kAug>
+//
+// kMulti (tt_lahc_multi.hip, include/ttga_lahc_multi.h): wave q of the launch is walker
+// q % walkers of row q / walkers. It reads the row and rng[p] like any other walk, jumps to
+// its own stretch of the stream, and writes to `work` only: its numbers, its exit row when
+// it improved, and (the last walker) the stream state behind all of them. Everything it
+// needs stands under `if constexpr (kMulti)`, so the other kernels compile to the
+// instructions they had.
+template <bool kAug, bool kMulti = false>
 __device__ __forceinline__ void lahc_kempe_walk(const DevProblem& pb, uint8_t* __restrict__ slot,
                                                 uint8_t* __restrict__ room, int64_t* __restrict__ rng, int P, int steps,
                                                 int L, double p_swap, double p_kempe, double kempe_from, int max_chain,
                                                 int room_rule, int32_t* __restrict__ scv, int32_t* __restrict__ penalty,
                                                 int32_t* __restrict__ gain, int32_t* __restrict__ accepted,
-                                                int32_t* __restrict__ best_step, int32_t* __restrict__ kstats) {
+                                                int32_t* __restrict__ best_step, int32_t* __restrict__ kstats,
+                                                int walkers = 1, void* work = nullptr) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     constexpr int kStats = kAug ? 7 : 5;
     const int E = pb.E, R = pb.R, S = pb.S, EW64 = pb.EW64, lane = threadIdx.x;
-    const long p = blockIdx.x;
+    const long q = blockIdx.x;                          // the launch's wave
+    const long p = kMulti ? q / walkers : q;            // its row
     if (p >= P) return;
     uint64_t* set = (uint64_t*)lds;
     uint64_t* occ = set + (size_t)kSlots * EW64;
@@ -138,6 +178,11 @@ __device__ __forceinline__ void lahc_kempe_walk(const DevProblem& pb, uint8_t* _
         __syncthreads();
     }
     if (bad_row || wave_any(hard) || steps == 0) {
+        if constexpr (kMulti) {                         // a closed row: zeros, the flag among them
+            if (lane < kLmNums) lahc_multi_work(work, P, walkers, E).nums[q * kLmNums + lane] = 0;
+            if (bad_row && lane == 0) atomicOr(pb.status, kStatusLahcBadGene);
+            return;
+        }
         if (lane == 0) {
             if (gain) gain[p] = 0;
             if (accepted) accepted[p] = 0;
@@ -150,6 +195,7 @@ __device__ __forceinline__ void lahc_kempe_walk(const DevProblem& pb, uint8_t* _
 
     // ---- the walk (cur and best relative to scv0)
     int64_t st = rng[p];
+    if constexpr (kMulti) st = lahc_multi_start(st, steps, (int)(q - p * walkers));
     int cur = 0, best = 0, n_acc = 0, b_step = 0;
     int k_tried = 0, k_capped = 0, k_noroom = 0, k_acc = 0, k_events = 0;
     [[maybe_unused]] int k_rescued = 0, k_displaced = 0;
@@ -511,6 +557,37 @@ __device__ __forceinline__ void lahc_kempe_walk(const DevProblem& pb, uint8_t* _
     }
 
     // ---- exit: the best row
+    if constexpr (kMulti) {
+        const LahcMultiWork mw = lahc_multi_work(work, P, walkers, E);
+        if (b_step > 0) {
+            const uint8_t* os = live_is_best ? sl : bsl;
+            const uint8_t* orr = live_is_best ? rr : brr;
+            uint8_t* row = mw.rows + (size_t)q * 2 * (size_t)E;
+            for (int e = lane; e < E; e += 64) {
+                row[e] = os[e];
+                row[E + e] = orr[e];
+            }
+        }
+        if (lane == 0) {
+            int32_t* nm = mw.nums + q * kLmNums;
+            nm[kLmGain] = -best;
+            nm[kLmAccepted] = n_acc;
+            nm[kLmBestStep] = b_step;
+            nm[kLmStats + 0] = k_tried;
+            nm[kLmStats + 1] = k_capped;
+            nm[kLmStats + 2] = k_noroom;
+            nm[kLmStats + 3] = k_acc;
+            nm[kLmStats + 4] = k_events;
+            if constexpr (kAug) {
+                nm[kLmStats + 5] = k_rescued;
+                nm[kLmStats + 6] = k_displaced;
+            }
+            nm[kLmWalked] = 1;
+            nm[kLmWalked + 1] = 0;
+            if (q - p * walkers == walkers - 1) mw.state[p] = st;     // s_K: the row's stream behind every walker
+        }
+        return;
+    }
     if (b_step > 0) {
         const uint8_t* os = live_is_best ? sl : bsl;
         const uint8_t* orr = live_is_best ? rr : brr;

@@ -14,6 +14,7 @@
 //           [--report] [--unique] [--init random|greedy] [--kempe P] [--kempe-max-chain N]
 //           [--slot-swap N] [--lahc N] [--lahc-history L] [--lahc-swap P]
 //           [--lahc-kempe P] [--lahc-kempe-max-chain N] [--lahc-kempe-rooms direct|augment]
+//           [--lahc-walkers K]
 //           [--crossover uniform|guided] [--crossover-repair]
 //
 // --crossover guided: every sub-batch is bred by tt_ga_breed_guided
@@ -46,6 +47,14 @@
 // tt_lahc_kempe: a chain event with no free possible room moves the target
 // slot's holders along an augmenting path. The lahcKempe line then also carries
 // "rescued" and "displaced". The default is direct: no new call.
+//
+// --lahc-walkers K (1 .. 1024, needs --lahc; the default is 1: no new call): with K > 1 the
+// walk is tt_lahc_multi (include/ttga_lahc_multi.h) with the walk's other flags: K walks
+// from every row, each on its own stretch of the row's stream, the best one kept. The lahc
+// and lahcKempe lines then describe the winners' walks, and each island prints one
+// {"lahcWalkers": {"gain", "gainFirst", "rows", "walkers", "winnerLater"}} line after them
+// (ttga.islands prints the same): the rows that walked, the winners' gain, walker 0's gain
+// on the same rows (the single walk's) and the rows another walker won.
 //
 // --slot-swap N: tt_slot_swap (include/ttga_slotswap.h) with max_passes N runs
 // directly behind every tt_local_search_eval, on the same stream, and lowers
@@ -164,6 +173,7 @@ struct Stages {
     double lahc_kempe = 0.0;                      // --lahc-kempe: tt_lahc_kempe's share of chains (0: tt_lahc)
     int lahc_kempe_max_chain = 0;                 // --lahc-kempe-max-chain (0: no cap)
     bool lahc_kempe_augment = false;              // --lahc-kempe-rooms augment: tt_lahc_kempe_aug, room_rule 1
+    int lahc_walkers = 1;                         // --lahc-walkers: tt_lahc_multi's walkers (1: the calls above)
     bool guided = false;                          // --crossover guided: tt_ga_breed_guided breeds
     bool cx_repair = false;                       // --crossover-repair
 };
@@ -259,6 +269,8 @@ Control parse_control(int argc, char** argv) {
              s.lahc_kempe_max_chain);
     take_choice(args, "--lahc-kempe-rooms", "direct", "augment", "--lahc-kempe-rooms must be direct or augment",
                 s.lahc_kempe_augment);
+    take_int(args, "--lahc-walkers", 1, "--lahc-walkers must be an integer from 1 to 1024", s.lahc_walkers);
+    if (s.lahc_walkers > 1024) bad_flag("--lahc-walkers must be an integer from 1 to 1024");
     s.cx_repair = take_flag(args, "--crossover-repair");
     take_choice(args, "--crossover", "uniform", "guided", "--crossover must be uniform or guided", s.guided);
     if (s.cx_repair && !s.guided) bad_flag("--crossover-repair needs --crossover guided");
@@ -266,6 +278,7 @@ Control parse_control(int argc, char** argv) {
     if (s.lahc_kempe > 0 && !(s.lahc_swap <= 1.0 - s.lahc_kempe))         // tt_lahc_kempe's own test
         bad_flag("--lahc-swap and --lahc-kempe must not add up to more than 1");
     if (s.lahc_kempe_augment && !(s.lahc_kempe > 0)) bad_flag("--lahc-kempe-rooms augment needs --lahc-kempe");
+    if (s.lahc_walkers > 1 && s.lahc <= 0) bad_flag("--lahc-walkers needs --lahc");
     for (const char* k : {"--gpus", "--islands", "--pop", "--generations", "--children", "--stagger-parts"}) {
         auto it = std::find(args.begin(), args.end(), k);
         if (it != args.end()) {
@@ -679,7 +692,14 @@ struct Island {
     // batch schedule: part[0] = {0, C, st, its work buffer}, each sub-batch replaced behind its own
     // search, and neither ev_op nor another stream or work buffer exists
     int parts = 1;
-    struct Part { int off = 0, n = 0; hipStream_t s = nullptr; void* work = nullptr; };
+    // lw_work, lw_gain: --lahc-walkers' work buffer and walker gains [rows][K] of the part's stream
+    struct Part {
+        int off = 0, n = 0;
+        hipStream_t s = nullptr;
+        void* work = nullptr;
+        void* lw_work = nullptr;
+        int32_t* lw_gain = nullptr;
+    };
     std::vector<Part> part;
     hipEvent_t ev_op = nullptr;                       // behind the last population operation (parts > 1)
     hipStream_t op_stream = nullptr;                  // the stream that operation ran on
@@ -696,9 +716,10 @@ struct Island {
     RunLog<2> swap_log;                               // --slot-swap: every searched row's gain and passes
     RunLog<2> lahc_log;                               // --lahc: every searched row's gain, accepted and feasible flag
     // --lahc-kempe: every searched row's lk_width() counts, row-major (five; seven under
-    // --lahc-kempe-rooms augment)
+    // --lahc-kempe-rooms augment and under --lahc-walkers, whose call writes seven)
     RunLog<7> lk_log;
-    int lk_width() const { return stage.lahc_kempe_augment ? 7 : 5; }
+    int lk_width() const { return stage.lahc_kempe_augment || stage.lahc_walkers > 1 ? 7 : 5; }
+    RunLog<2> lw_log;                                 // --lahc-walkers: every searched row's winner and walker 0's gain
     RunLog<2> cx_log;                                 // --crossover guided: every child's cost, repaired and flags
     int32_t* ev_order = nullptr;                      // event_order()'s, once computed
 
@@ -746,6 +767,7 @@ struct Island {
         if (stage.slot_swap > 0) swap_log.alloc(N + bred, "timeslot-swap rows");          // the members too
         if (stage.lahc > 0) lahc_log.alloc(N + bred, "late-acceptance rows", true);       // the members too
         if (stage.lahc_kempe > 0) lk_log.alloc(N + bred, "late-acceptance rows");
+        if (stage.lahc_walkers > 1) lw_log.alloc(N + bred, "late-acceptance rows");
         if (stage.guided) {
             cx_log.alloc(bred, "guided crossovers", true);
             event_order();                            // before any part's stream breeds in it
@@ -763,6 +785,12 @@ struct Island {
             off += part[j].n;
             if (j > 0) check_hip(hipStreamCreateWithFlags(&part[j].s, hipStreamNonBlocking), "hipStreamCreate");
             check_hip(hipMalloc(&part[j].work, work_bytes(part[j].n)), "hipMalloc");
+            if (stage.lahc_walkers > 1) {               // once: the first part's stream walks the members too
+                const int rows = j == 0 ? std::max(part[j].n, N) : part[j].n;
+                check_hip(hipMalloc(&part[j].lw_work, std::max<size_t>(tt_lahc_multi_work_bytes(tp, rows, stage.lahc_walkers), 16)),
+                          "hipMalloc");
+                check_hip(hipMalloc(&part[j].lw_gain, 4 * (size_t)rows * stage.lahc_walkers), "hipMalloc");
+            }
         }
         work = part[0].work;
     }
@@ -923,7 +951,24 @@ struct Island {
     // search, evaluation and timeslot swap; their scv and penalty are lowered in place
     void late_acceptance(const Pop& r, int64_t* g, hipStream_t s) {
         const long at = lahc_log.reserve(r.n);
-        if (stage.lahc_kempe > 0 && stage.lahc_kempe_augment) {
+        if (stage.lahc_walkers > 1) {
+            // the walk the branches below would call: without chains p_kempe 0 and room_rule 0
+            const Part* q = &part[0];
+            for (const Part& x : part)
+                if (x.s == s) q = &x;
+            const int K = stage.lahc_walkers;
+            if (stage.lahc_kempe > 0) lk_log.reserve(r.n);
+            const long aw = lw_log.reserve(r.n);        // row for row with lahc_log
+            check_tt(tt_lahc_multi(tp, r.slot, r.room, g, r.n, K, stage.lahc, stage.lahc_history, stage.lahc_swap,
+                                   stage.lahc_kempe, stage.lahc_kempe_max_chain, stage.lahc_kempe_augment ? 1 : 0, r.scv,
+                                   r.penalty, lahc_log.col(0) + at, lahc_log.col(1) + at, nullptr,
+                                   stage.lahc_kempe > 0 ? lk_log.data + 7 * at : nullptr, lw_log.col(0) + aw, q->lw_gain,
+                                   q->lw_work, s),
+                     "tt_lahc_multi");
+            check_hip(hipMemcpy2DAsync(lw_log.col(1) + aw, 4, q->lw_gain, 4 * (size_t)K, 4, (size_t)r.n,
+                                       hipMemcpyDeviceToDevice, s),
+                      "hipMemcpy2DAsync");
+        } else if (stage.lahc_kempe > 0 && stage.lahc_kempe_augment) {
             lk_log.reserve(r.n);                      // row for row with lahc_log
             check_tt(tt_lahc_kempe_aug(tp, r.slot, r.room, g, r.n, stage.lahc, stage.lahc_history, stage.lahc_swap,
                                        stage.lahc_kempe, stage.lahc_kempe_max_chain, 1, r.scv, r.penalty,
@@ -983,6 +1028,26 @@ struct Island {
             k.obj["displaced"] = Json::I(sum[6]);
         }
         return wrap("lahcKempe", k);
+    }
+
+    // the --lahc-walkers line (ttga/ga.py lahc_walkers_line); lahc_log and lw_log go row for row
+    Json lahc_walkers_report() {
+        const auto h = read(lahc_log);
+        const auto w = read(lw_log);
+        long rows = 0, total = 0, first = 0, later = 0;
+        for (long i = 0; i < h.rows && i < w.rows; i++) {
+            rows += h.bytes[i] != 0;
+            total += h.col[0][i];
+            first += w.col[1][i];
+            later += w.col[0][i] > 0;
+        }
+        Json k;
+        k.obj["rows"] = Json::I(rows);
+        k.obj["walkers"] = Json::I(stage.lahc_walkers);
+        k.obj["gain"] = Json::I(total);
+        k.obj["gainFirst"] = Json::I(first);
+        k.obj["winnerLater"] = Json::I(later);
+        return wrap("lahcWalkers", k);
     }
 
     // LPT order (C >= kLptMinChildren), localSearch and evaluation of rows [off, off + n) on s
@@ -1174,9 +1239,12 @@ struct Island {
         swap_log.release();
         lahc_log.release();
         lk_log.release();
+        lw_log.release();
         cx_log.release();
         for (size_t j = 0; j < part.size(); j++) {
             if (part[j].work) (void)hipFree(part[j].work);
+            if (part[j].lw_work) (void)hipFree(part[j].lw_work);
+            if (part[j].lw_gain) (void)hipFree(part[j].lw_gain);
             if (j > 0 && part[j].s) (void)hipStreamDestroy(part[j].s);
         }
         if (ev_op) (void)hipEventDestroy(ev_op);
@@ -1366,6 +1434,7 @@ int main(int argc, char** argv) {
     each_island(ctl.stage.slot_swap > 0, [](Island& I, int) { return I.slot_swap_report(); });
     each_island(ctl.stage.lahc > 0, [](Island& I, int) { return I.lahc_report(); });
     each_island(ctl.stage.lahc_kempe > 0, [](Island& I, int) { return I.lahc_kempe_report(); });
+    each_island(ctl.stage.lahc_walkers > 1, [](Island& I, int) { return I.lahc_walkers_report(); });
     each_island(ctl.report, [](Island& I, int k) { return I.report(k, k); });
     out.line(run_final_line(K, C, seconds_since(t_start)));
     for (int k = 0; k < K; k++) {

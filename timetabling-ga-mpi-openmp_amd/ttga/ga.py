@@ -182,6 +182,8 @@ _TALLIED = {
     "lahc": ("lahc > 0", "rows", ("gain", "accepted", "best_step"), ("searched", "improved", "accepted", "gain"), True),
     "lahc_kempe": ("lahc_kempe > 0", "rows", ("stats",), ("tried", "capped", "no_room", "accepted", "chain_events"),
                    True),
+    "lahc_walkers": ("lahc_walkers > 1", None, ("winner", "walker_gain"), ("rows", "gain", "gainFirst", "winnerLater"),
+                     True),
     "cx": ("crossover='guided'", "children", ("cost", "repaired"), ("crossed", "clean", "cost", "repaired"), False),
 }
 
@@ -192,9 +194,11 @@ class Tally:
     up on the stream behind each call, and on the host the `rows` it was called
     on. The tensors join `register` (Island's record_stream pass)."""
 
-    def __init__(self, n: int, outputs, sums, dev, register: list):
+    def __init__(self, n: int, outputs, sums, dev, register: list, walkers: int = 1):
         import torch
-        self.out = {k: torch.zeros((n, len(sums)) if k == "stats" else n, dtype=torch.int32, device=dev)
+        # the outputs with more than one entry a row (tt_lahc_multi writes seven counts whatever the room rule)
+        wide = {"stats": 7 if walkers > 1 else len(sums), "walker_gain": walkers}
+        self.out = {k: torch.zeros((n, wide[k]) if k in wide else n, dtype=torch.int32, device=dev)
                     for k in outputs}
         self.sums = torch.zeros(len(sums), dtype=torch.int64, device=dev)
         self.rows = 0
@@ -284,6 +288,14 @@ class Island(Members):
     slot's holders along an augmenting path. lahc_kempe_stats() then also has
     `rescued` and `displaced`. "direct" calls what the island called before.
 
+    lahc_walkers=K > 1 (needs lahc > 0): the walk is tt_lahc_multi
+    (include/ttga_lahc_multi.h) with the island's walk arguments: K walks from
+    every searched row, each on its own stretch of the row's stream, and the
+    best of them comes back. lahc_stats() and lahc_kempe_stats() then describe
+    the winners' walks, and lahc_walkers_stats() compares the winners with
+    walker 0, which is the single walk. lahc_walkers=1 issues exactly the calls
+    the island issued before.
+
     crossover="guided": every sub-batch is bred with tt_ga_breed_guided
     (include/ttga_cx.h) in place of tt_ga_breed, on the same stream and at the
     same place in the operation chain, in the handle's greedy_order(); with
@@ -302,7 +314,8 @@ class Island(Members):
                  kempe: float = 0.0, kempe_max_chain: int = 0, slot_swap: int = 0,
                  lahc: int = 0, lahc_history: int = 500, lahc_swap: float = 0.5,
                  crossover: str = "uniform", crossover_repair: bool = False,
-                 lahc_kempe: float = 0.0, lahc_kempe_max_chain: int = 0, lahc_kempe_rooms: str = "direct"):
+                 lahc_kempe: float = 0.0, lahc_kempe_max_chain: int = 0, lahc_kempe_rooms: str = "direct",
+                 lahc_walkers: int = 1):
         """stream: a torch.cuda.Stream of the island's own, or None (torch's current
         stream). Islands multiplexed on one GPU (ttga.islands --islands K) each take
         one, so one island's launches fill the SIMD slots another's local-search tail
@@ -310,7 +323,7 @@ class Island(Members):
         synchronises its stream first, and a caller that moves data between islands
         (migration) synchronises the device around it."""
         validate(init, kempe, kempe_max_chain, slot_swap, lahc, lahc_history, lahc_swap, crossover, crossover_repair,
-                 lahc_kempe, lahc_kempe_max_chain, lahc_kempe_rooms)
+                 lahc_kempe, lahc_kempe_max_chain, lahc_kempe_rooms, lahc_walkers)
         import torch
         if not (1 <= children <= pop_size):
             raise ValueError("need 1 <= children <= pop_size")
@@ -338,6 +351,7 @@ class Island(Members):
         self.lahc, self.lahc_history, self.lahc_swap = int(lahc), int(lahc_history), float(lahc_swap)
         self.lahc_kempe, self.lahc_kempe_max_chain = float(lahc_kempe), int(lahc_kempe_max_chain)
         self.lahc_kempe_rooms = lahc_kempe_rooms
+        self.lahc_walkers = int(lahc_walkers)
         self.crossover, self.crossover_repair = crossover, bool(crossover_repair)
         self.generation = 0
         self.schedule = schedule
@@ -379,15 +393,26 @@ class Island(Members):
         self.on = {stage for stage, on in (("unique", self.unique), ("kempe", self.kempe > 0),
                                            ("slot_swap", self.slot_swap > 0), ("lahc", self.lahc > 0),
                                            ("lahc_kempe", self.lahc_kempe > 0),
+                                           ("lahc_walkers", self.lahc_walkers > 1),
                                            ("cx", self.crossover == "guided")) if on}
         self._init_tally = {}
         for stage, (_, _, outputs, _, in_init) in _TALLIED.items():
             if stage in self.on:
                 sums = self._sum_names(stage)
                 if in_init:
-                    self._init_tally[stage] = Tally(self.N, outputs, sums, dev, self._extra)
+                    self._init_tally[stage] = Tally(self.N, outputs, sums, dev, self._extra, self.lahc_walkers)
                 for p in self._parts:
-                    p.tally[stage] = Tally(p.n, outputs, sums, dev, self._extra)
+                    p.tally[stage] = Tally(p.n, outputs, sums, dev, self._extra, self.lahc_walkers)
+        # tt_lahc_multi's work buffers, allocated once: one per part (the parts run on streams
+        # of their own), the first of them large enough for the members too, whose walk runs
+        # on the first part's stream
+        if "lahc_walkers" in self.on:
+            for j, p in enumerate(self._parts):
+                rows = max(p.n, self.N) if j == 0 else p.n
+                p.tally["lahc_walkers"].work = torch.empty(dp.lahc_multi_work_bytes(rows, self.lahc_walkers),
+                                                           dtype=torch.uint8, device=dev)
+                self._extra.append(p.tally["lahc_walkers"].work)
+            self._init_tally["lahc_walkers"].work = self._parts[0].tally["lahc_walkers"].work
         self._replaced = 0
         self._pending = []                            # parts searched but not yet replaced, in breed order
         self._last_replace = 0                        # part whose work buffer holds the last replace's source
@@ -601,7 +626,21 @@ class Island(Members):
         t = tally["lahc"]
         gain, accepted = t.out["gain"], t.out["accepted"]
         n = int(rows["slot"].shape[0])
-        if self.lahc_kempe > 0 and self.lahc_kempe_rooms == "augment":
+        if self.lahc_walkers > 1:
+            # tt_lahc_multi with the walk the island would call: without chains p_kempe 0 and
+            # room_rule 0, which is tt_lahc's walk
+            tw, tk = tally["lahc_walkers"], tally.get("lahc_kempe")
+            winner, first = tw.out["winner"], tw.out["walker_gain"]
+            self.dp.lahc_multi(rows["slot"], rows["room"], rng, self.lahc_walkers, self.lahc, self.lahc_history,
+                               self.lahc_swap, self.lahc_kempe, self.lahc_kempe_max_chain,
+                               int(self.lahc_kempe_rooms == "augment"), scv=rows["scv"], penalty=rows["penalty"],
+                               gain=gain, accepted=accepted, best_step=t.out["best_step"],
+                               kempe_stats=tk.out["stats"] if tk else None, winner=winner, walker_gain=first,
+                               work=tw.work)
+            if tk:
+                tk.add(n, *tk.out["stats"][:, :len(tk.sums)].sum(dim=0).unbind())
+            tw.add(0, (rows["feasible"] != 0).sum(), gain.sum(), first[:, 0].sum(), (winner > 0).sum())
+        elif self.lahc_kempe > 0 and self.lahc_kempe_rooms == "augment":
             tk = tally["lahc_kempe"]
             self.dp.lahc_kempe_aug(rows["slot"], rows["room"], rng, self.lahc, self.lahc_history, self.lahc_swap,
                                    self.lahc_kempe, self.lahc_kempe_max_chain, 1, scv=rows["scv"],
@@ -639,7 +678,8 @@ class Island(Members):
         self.sync()
         holders = [t[stage] for t in [self._init_tally] + [p.tally for p in self._parts] if stage in t]
         totals = sum(t.sums.cpu() for t in holders).tolist()
-        return {count: sum(t.rows for t in holders), **{k: int(v) for k, v in zip(names, totals)}}
+        out = {k: int(v) for k, v in zip(names, totals)}
+        return {count: sum(t.rows for t in holders), **out} if count else out
 
     def cx_stats(self) -> dict:
         """Island(crossover="guided"): the children bred, how many of them
@@ -660,6 +700,13 @@ class Island(Members):
         lahc_kempe_rooms="augment" also the candidates a path `rescued` and the
         bystanders the accepted chains `displaced`."""
         return self._stats("lahc_kempe")
+
+    def lahc_walkers_stats(self) -> dict:
+        """Island(lahc_walkers > 1): the `rows` that walked, the `walkers` a
+        row, the winners' `gain`, `gainFirst`: the gain of walker 0 summed over
+        the same rows, which is what the single walk gets from them, and
+        `winnerLater`: the rows won by another walker than 0."""
+        return {**self._stats("lahc_walkers"), "walkers": self.lahc_walkers}
 
     def slot_swap_stats(self) -> dict:
         """Island(slot_swap > 0): the rows tt_slot_swap was called on, how many
@@ -890,6 +937,11 @@ def lahc_kempe_line(stats: dict) -> str:
     return json_line({"lahcKempe": line})
 
 
+def lahc_walkers_line(stats: dict) -> str:
+    """The drivers' --lahc-walkers line of one island: Island.lahc_walkers_stats()."""
+    return json_line({"lahcWalkers": {k: int(stats[k]) for k in ("gain", "gainFirst", "rows", "walkers", "winnerLater")}})
+
+
 def crossover_line(stats: dict) -> str:
     """The drivers' --crossover guided line of one island: Island.cx_stats()
     with the mean cost of the crossed children (0 when none crossed)."""
@@ -915,4 +967,5 @@ STAGE_LINES = (
     ("slot_swap", False, lambda isl, proc, k: slot_swap_line(isl.slot_swap_stats())),
     ("lahc", False, lambda isl, proc, k: lahc_line(isl.lahc_stats())),
     ("lahc_kempe", False, lambda isl, proc, k: lahc_kempe_line(isl.lahc_kempe_stats())),
+    ("lahc_walkers", False, lambda isl, proc, k: lahc_walkers_line(isl.lahc_walkers_stats())),
 )

@@ -49,6 +49,12 @@ Reference correspondence:
   chain's rooms by augmenting paths, ttga.ga.Island(lahc_kempe_rooms="augment");
   the lahcKempe line then also carries the chains a path rescued and the
   bystanders displaced; the default is direct, which issues no new call),
+  `--lahc-walkers K` (with --lahc N; K > 1: the walk is tt_lahc_multi,
+  include/ttga_lahc_multi.h, K walks from every row of which the best is kept,
+  ttga.ga.Island(lahc_walkers=K); each island then prints a `lahcWalkers` line
+  after the lahc lines: the rows that walked, the walkers, the winners' gain,
+  walker 0's gain on the same rows and the rows another walker won; the
+  default is 1, which issues no new call),
   `--crossover uniform|guided` / `--crossover-repair` (guided: the children are
   bred by tt_ga_breed_guided, include/ttga_cx.h, ttga.ga.Island(crossover=
   "guided", crossover_repair=...); each island then prints a `crossover` line
@@ -125,6 +131,9 @@ def parse_control(argv, out=sys.stdout, err=sys.stderr) -> dict:
             raise SystemExit(1)
     if extra.get("lahc_kempe_rooms") == "augment" and not extra.get("lahc_kempe", 0) > 0:
         err.write(f"Error: {stages.LAHC_KEMPE_ROOMS_NEEDS_KEMPE}\n")
+        raise SystemExit(1)
+    if extra.get("lahc_walkers", 1) > 1 and not extra.get("lahc", 0) > 0:
+        err.write(f"Error: {stages.LAHC_WALKERS_NEEDS_LAHC}\n")
         raise SystemExit(1)
     if len(args) % 2 != 0:
         err.write("Parse error: Number of command line parameters incorrect\nUsage:\n" + USAGE + "\n")

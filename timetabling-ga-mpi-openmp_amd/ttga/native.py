@@ -53,6 +53,10 @@ LAHC_KEMPE_EXPORTS = ("tt_lahc_kempe",)
 LAHC_KEMPE_AUG_EXPORTS = ("tt_lahc_kempe_aug",)
 ROOM_RULES = ("direct", "augment")          # tt_lahc_kempe_aug's room_rule 0 and 1
 
+# include/ttga_lahc_multi.h (brought in by ttga_lahc.h)
+LAHC_MULTI_EXPORTS = ("tt_lahc_multi_work_bytes", "tt_lahc_multi")
+MAX_WALKERS = 1024                          # tt_lahc_multi's walkers: 1 .. 1024
+
 # include/ttga_cx.h
 CX_EXPORTS = ("tt_crossover_guided", "tt_ga_breed_guided")
 
@@ -131,6 +135,11 @@ def load(path: os.PathLike | str | None = None) -> ctypes.CDLL:
     lib.tt_lahc_kempe.restype = ctypes.c_int
     lib.tt_lahc_kempe_aug.argtypes = [vp, vp, vp, vp, i32, i32, i32, dbl, dbl, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.tt_lahc_kempe_aug.restype = ctypes.c_int
+    lib.tt_lahc_multi_work_bytes.argtypes = [vp, i32, i32]
+    lib.tt_lahc_multi_work_bytes.restype = ctypes.c_size_t
+    lib.tt_lahc_multi.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, dbl, dbl, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                  vp, vp]
+    lib.tt_lahc_multi.restype = ctypes.c_int
     lib.tt_crossover_guided.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]
     lib.tt_crossover_guided.restype = ctypes.c_int
     lib.tt_ga_breed_guided.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, dbl, dbl, i32, i32, vp, vp, vp, vp, vp, vp]
@@ -567,6 +576,52 @@ class DeviceProblem:
                                                     int(max_chain), int(room_rule), ptr(scv), ptr(penalty), ptr(gain),
                                                     ptr(accepted), ptr(best_step), ptr(kempe_stats),
                                                     self._stream(slot)))
+
+    # -- parallel walkers of the walk (include/ttga_lahc_multi.h) -----------------------
+    def lahc_multi_work_bytes(self, P: int, walkers: int) -> int:
+        """tt_lahc_multi_work_bytes: the bytes of lahc_multi()'s work tensor for
+        P rows of `walkers` walkers; 0 for arguments the call refuses."""
+        if not (0 <= int(P) < 2 ** 31 and -2 ** 31 <= int(walkers) < 2 ** 31):
+            return 0
+        return int(self.lib.tt_lahc_multi_work_bytes(self.handle, int(P), int(walkers)))
+
+    def lahc_multi(self, slot, room, rng, walkers, steps, history, p_swap=0.25, p_kempe=0.5, max_chain=0, room_rule=1,
+                   scv=None, penalty=None, gain=None, accepted=None, best_step=None, kempe_stats=None, winner=None,
+                   walker_gain=None, work=None):
+        """tt_lahc_multi in place on slot, room [P, E] and rng [P]: `walkers`
+        walks of lahc_kempe_aug() from every feasible row, each on its own
+        stretch of the row's stream; the best of them comes back and rng moves
+        3 * steps * walkers draws on. The optional tensors are
+        lahc_kempe_aug()'s (they describe the winner's walk), winner int32 [P]
+        and walker_gain int32 [P, walkers]. work: a uint8 CUDA tensor of at
+        least lahc_multi_work_bytes(P, walkers) bytes; it may be None with
+        walkers == 1, and with more walkers None allocates one for the call."""
+        import torch
+        P = self._pop(slot, room)
+        self._rng(rng, P)
+        K = int(walkers)
+        for name, t, n, what in (("scv", scv, P, "P"), ("penalty", penalty, P, "P"), ("gain", gain, P, "P"),
+                                 ("accepted", accepted, P, "P"), ("best_step", best_step, P, "P"),
+                                 ("kempe_stats", kempe_stats, 7 * P, "7 P"), ("winner", winner, P, "P"),
+                                 ("walker_gain", walker_gain, max(K, 0) * P, "P * walkers")):
+            if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n
+                                      and t.device == slot.device):
+                raise ValueError(f"{name} must be a contiguous int32 CUDA tensor of {what} entries "
+                                 "on the population's device")
+        if work is None and 1 < K <= MAX_WALKERS and P * K < 2 ** 31:
+            work = torch.empty(self.lahc_multi_work_bytes(P, K), dtype=torch.uint8, device=slot.device)
+        if work is not None:
+            need = self.lahc_multi_work_bytes(P, K)
+            if not (work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous() and work.device == slot.device
+                    and (work.numel() >= need or need == 0)):
+                raise ValueError(f"work must be a contiguous uint8 CUDA tensor of at least {need} bytes "
+                                 "on the population's device")
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)    # noqa: E731
+        _check(self.lib, self.lib.tt_lahc_multi(self.handle, slot.data_ptr(), room.data_ptr(), rng.data_ptr(), P, K,
+                                                int(steps), int(history), float(p_swap), float(p_kempe),
+                                                int(max_chain), int(room_rule), ptr(scv), ptr(penalty), ptr(gain),
+                                                ptr(accepted), ptr(best_step), ptr(kempe_stats), ptr(winner),
+                                                ptr(walker_gain), ptr(work), self._stream(slot)))
 
     # -- conflict-guided crossover (include/ttga_cx.h) -------------------------------
     def _cx_args(self, slot, order, P, cost, repaired):

@@ -39,6 +39,9 @@ FLAGS = (
          "--lahc-kempe-rooms must be direct or augment",
          "the room rule of the walk's chains: tt_lahc_kempe's direct one, or augmenting paths, tt_lahc_kempe_aug "
          "(Island(lahc_kempe_rooms=...))"),
+    Flag("--lahc-walkers", "lahc_walkers", "int", (1, 1024), "--lahc-walkers must be an integer from 1 to 1024",
+         "walks from every row, each on its own stretch of the row's stream, the best one kept: tt_lahc_multi "
+         "(Island(lahc_walkers=...)); 1: the single walk"),
     Flag("--crossover-repair", "crossover_repair", "flag", None, None,
          "guided: an event that clashes in both parents' slots goes to a slot of least cost"),
     Flag("--crossover", "crossover", "choice", ("uniform", "guided"), "--crossover must be uniform or guided",
@@ -56,6 +59,10 @@ LAHC_KEMPE_SHARES = "--lahc-swap and --lahc-kempe must not add up to more than 1
 LAHC_KEMPE_ROOMS_NEEDS_KEMPE = "--lahc-kempe-rooms augment needs --lahc-kempe"
 
 
+# and where --lahc-walkers comes without the walk
+LAHC_WALKERS_NEEDS_LAHC = "--lahc-walkers needs --lahc"
+
+
 def lahc_kempe_error(lahc, lahc_swap, lahc_kempe):
     """The message for a --lahc-kempe that does not go with --lahc and
     --lahc-swap (the values in force, defaults included), or None."""
@@ -67,7 +74,7 @@ def lahc_kempe_error(lahc, lahc_swap, lahc_kempe):
 
 
 def validate(init, kempe, kempe_max_chain, slot_swap, lahc, lahc_history, lahc_swap, crossover, crossover_repair,
-             lahc_kempe=0.0, lahc_kempe_max_chain=0, lahc_kempe_rooms="direct"):
+             lahc_kempe=0.0, lahc_kempe_max_chain=0, lahc_kempe_rooms="direct", lahc_walkers=1):
     """Island's stage arguments: the first one out of range raises ValueError."""
     for ok, message in (
             (crossover in ("uniform", "guided"), "crossover must be 'uniform' or 'guided'"),
@@ -85,7 +92,9 @@ def validate(init, kempe, kempe_max_chain, slot_swap, lahc, lahc_history, lahc_s
             (not float(lahc_kempe) > 0 or float(lahc_swap) <= 1.0 - float(lahc_kempe),
              "lahc_swap + lahc_kempe must be <= 1"),
             (lahc_kempe_rooms in ("direct", "augment"), "lahc_kempe_rooms must be 'direct' or 'augment'"),
-            (lahc_kempe_rooms != "augment" or float(lahc_kempe) > 0, "lahc_kempe_rooms='augment' needs lahc_kempe > 0")):
+            (lahc_kempe_rooms != "augment" or float(lahc_kempe) > 0, "lahc_kempe_rooms='augment' needs lahc_kempe > 0"),
+            (1 <= int(lahc_walkers) <= 1024, "lahc_walkers must be from 1 to 1024"),
+            (int(lahc_walkers) == 1 or int(lahc) > 0, "lahc_walkers > 1 needs lahc > 0")):
         if not ok:
             raise ValueError(message)
 

@@ -58,7 +58,10 @@ tt_lahc_kempe (include/ttga_lahc_kempe.h, Island(lahc_kempe=P,
 lahc_kempe_max_chain=N)); "lahc" then also carries the share, the cap and the
 chains tried, capped, without a room and accepted and their mean length; with
 --lahc-kempe-rooms augment (tt_lahc_kempe_aug, include/ttga_lahc_kempe_aug.h)
-also the rule, the chains a path rescued and the bystanders displaced.
+also the rule, the chains a path rescued and the bystanders displaced. With
+--lahc-walkers K (tt_lahc_multi, include/ttga_lahc_multi.h,
+Island(lahc_walkers=K)) "lahc" carries "walkers": K, the rows that walked, the
+winners' gain, walker 0's gain on the same rows and the rows another walker won.
 --crossover guided runs Island(crossover="guided", crossover_repair=...):
 tt_ga_breed_guided (include/ttga_cx.h) breeds in place of tt_ga_breed; the
 record then carries "crossover" (the repair flag, the children, how many
@@ -221,6 +224,10 @@ def run_ga(a):
             if a.lahc_kempe_rooms == "augment":       # tt_lahc_kempe_aug's two more counts
                 out["lahc"]["kempe"].update(rooms="augment", rescued=sum(s["rescued"] for s in stats),
                                             displaced=sum(s["displaced"] for s in stats))
+    if a.lahc > 0 and a.lahc_walkers > 1:
+        stats = [i.lahc_walkers_stats() for i in isls]
+        out["lahc"]["walkers"] = {"walkers": a.lahc_walkers, **{k: sum(s[k] for s in stats)
+                                                                  for k in ("rows", "gain", "gainFirst", "winnerLater")}}
     if a.crossover == "guided":
         stats = [i.cx_stats() for i in isls]
         k = {key: sum(s[key] for s in stats) for key in ("children", "crossed", "clean", "cost", "repaired")}

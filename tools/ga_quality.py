@@ -66,6 +66,14 @@ island with the direct rule, same seeds, flags and parameters, no reference
 run; per run the walk's counts and the chains' (with the rule also those a
 path rescued and the bystanders displaced).
 
+--lahc N --lahc-walkers K (with any of the walk's other flags) compares the
+walk's parallel walkers: Island(lahc_walkers=K) (tt_lahc_multi,
+include/ttga_lahc_multi.h: K walks from every row, the best one kept) against
+the same island with the single walk, same seeds, flags and parameters, no
+reference run; per run the walk's counts, and with the walkers the winners'
+gain next to walker 0's on the same rows (`gain`, `gain_first`) and the share
+of rows another walker won.
+
 --crossover guided [--crossover-repair] does the same for the conflict-guided
 crossover: Island(crossover="guided", crossover_repair=...) (tt_ga_breed_guided,
 include/ttga_cx.h) against the island without it, same seeds and parameters, no
@@ -105,7 +113,7 @@ def summarize(final, feas, trace, checkpoints):
 def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch", unique=False, stats_out=None,
                 init="random", kempe=0.0, kempe_max_chain=0, slot_swap=0, lahc=0, lahc_history=500,
                 lahc_swap=0.5, crossover="uniform", crossover_repair=False, lahc_kempe=0.0,
-                lahc_kempe_max_chain=0, lahc_kempe_rooms="direct"):
+                lahc_kempe_max_chain=0, lahc_kempe_rooms="direct", lahc_walkers=1):
     import torch
 
     from ttga import native, stages
@@ -145,6 +153,8 @@ def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch", uni
                 stats_out.append(getattr(isl, stage + "_stats")())
                 if stage == "lahc" and "lahc_kempe" in isl.on:
                     stats_out[-1] = dict(stats_out[-1], kempe=isl.lahc_kempe_stats())
+                if stage == "lahc" and "lahc_walkers" in isl.on:
+                    stats_out[-1] = dict(stats_out[-1], walkers=isl.lahc_walkers_stats())
             else:            # the plain island's distinct genomes, for the comparison
                 first = dp.genome_first(isl.pop["slot"], isl.pop["room"])
                 stats_out.append({"distinct": int((first == torch.arange(pop, dtype=torch.int32, device="cuda")).sum())})
@@ -206,6 +216,7 @@ def main():
         "crossover": f"guided: compare Island(crossover='guided') {without}",
         "lahc_kempe": f"P > 0 (with --lahc N): compare Island(lahc=N, lahc_kempe=P) with Island(lahc=N)",
         "lahc_kempe_rooms": "augment (with --lahc N --lahc-kempe P): compare the room rules, same flags otherwise",
+        "lahc_walkers": "K > 1 (with --lahc N): compare Island(lahc_walkers=K) with the single walk, same flags otherwise",
         "lahc_history": None, "lahc_swap": None, "crossover_repair": None, "lahc_kempe_max_chain": None})
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -264,6 +275,24 @@ def main():
                    ("median_kempe", "median_plain"), extras)
     if a.lahc_kempe_rooms == "augment" and not a.lahc_kempe > 0:
         raise SystemExit(stages.LAHC_KEMPE_ROOMS_NEEDS_KEMPE)
+    if a.lahc_walkers > 1:                           # K walkers against the single walk, everything else alike
+        message = stages.LAHC_WALKERS_NEEDS_LAHC if not a.lahc > 0 else (
+            stages.lahc_kempe_error(a.lahc, a.lahc_swap, a.lahc_kempe) if a.lahc_kempe > 0 else None)
+        if message:
+            raise SystemExit(message)
+        walk = dict(rest, lahc_kempe=a.lahc_kempe, lahc_kempe_max_chain=a.lahc_kempe_max_chain,
+                    lahc_kempe_rooms=a.lahc_kempe_rooms)
+        res.update(walk, lahc_walkers=a.lahc_walkers)
+
+        def extras(st, with_stage):
+            out = {"lahc_stats": st}
+            if with_stage:
+                w = [s["walkers"] for s in st]
+                out.update(gain=sum(x["gain"] for x in w), gain_first=sum(x["gainFirst"] for x in w),
+                           later_winner_share=sum(x["winnerLater"] for x in w) / max(1, sum(x["rows"] for x in w)))
+            return out
+        return run(("device_single", "device_walkers"), (walk, dict(walk, lahc_walkers=a.lahc_walkers)),
+                   "walkers_vs_single", ("median_walkers", "median_single"), extras, plain_stats=True)
     if a.lahc_kempe > 0:
         message = stages.lahc_kempe_error(a.lahc, a.lahc_swap, a.lahc_kempe)
         if message:
