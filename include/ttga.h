@@ -19,6 +19,18 @@
  * several host threads on different streams. Nothing here falls back to the
  * CPU: without a usable gfx950 device the calls fail with TT_ERR_DEVICE.
  *
+ * Buffers (this header and the ttga_*.h additions): a call reads and writes
+ * exactly the documented extent of each buffer -- P*E bytes of a [P][E] uint8
+ * array, 4*P of an int32[P], 8*P of rng, the tt_*_work_bytes value of a work
+ * buffer -- and never writes a const one. Placement: a uint8 buffer (slot,
+ * room, feasible, flags, keep, perm) may start at any byte address; an int32
+ * buffer is 4-byte aligned; rng and every `work` buffer are 8-byte aligned.
+ * Nothing more is assumed: where a kernel has a faster path for better-placed
+ * rows (tt_eval: slot rows at a multiple of 4 or 16 bytes with E a multiple of
+ * 4 or 16, slot and room rows at even addresses with E even) it checks the
+ * address and E and otherwise takes a byte-wise path with the same results.
+ * Rows are contiguous: row i starts E bytes after row i - 1.
+ *
  * Limits: 1 <= E <= 65535, 1 <= R <= 64, S >= 0, F >= 0; at most 256 events
  * share one timeslot inside tt_assign_rooms/tt_local_search (beyond that the
  * affected rooms are written as 255 and tt_device_status() reports it).
