@@ -140,6 +140,13 @@ __device__ __forceinline__ int wave_sum(int v) {
 __device__ __forceinline__ uint64_t ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 __device__ __forceinline__ bool wave_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0ull; }
 
+// A 64-bit value that every lane holds alike (one LDS address read by the whole wave,
+// say), as a scalar: loops and loads driven by it stay scalar.
+__device__ __forceinline__ uint64_t wave_uniform64(uint64_t v) {
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
+           (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+
 // Index of this thread's wave in the workgroup, as a wave-uniform (SGPR) value
 // so that loops and loads driven by it stay scalar.
 __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }

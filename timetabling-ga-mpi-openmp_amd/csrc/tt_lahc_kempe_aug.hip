@@ -4,8 +4,9 @@
 //                      possible room, a breadth-first search over the target slot's holders
 //                      moves them along an augmenting path
 // No counterpart in the reference; its call site is tt_lahc's. The walk is
-// tt_lahc_kempe_walk.h's with kAug, a kernel of its own next to lahc_kempe_kernel.
-#include "tt_lahc_kempe_walk.h"
+// tt_lahc_walk.h's lahc_chain_walk with kAug, in a translation unit of its own like
+// lahc_kempe_kernel.
+#include "tt_lahc_walk.h"
 
 namespace ttga {
 
@@ -17,7 +18,7 @@ __global__ __launch_bounds__(64) void lahc_kempe_aug_kernel(DevProblem pb, uint8
                                                             int32_t* __restrict__ gain, int32_t* __restrict__ accepted,
                                                             int32_t* __restrict__ best_step,
                                                             int32_t* __restrict__ kstats) {
-    lahc_kempe_walk<true>(pb, slot, room, rng, P, steps, L, p_swap, p_kempe, kempe_from, max_chain, room_rule, scv,
+    lahc_chain_walk<true>(pb, slot, room, rng, P, steps, L, p_swap, p_kempe, kempe_from, max_chain, room_rule, scv,
                           penalty, gain, accepted, best_step, kstats);
 }
 
@@ -29,26 +30,13 @@ extern "C" int tt_lahc_kempe_aug(const tt_problem* p, uint8_t* slot, uint8_t* ro
                                  int history, double p_swap, double p_kempe, int max_chain, int room_rule, int32_t* scv,
                                  int32_t* penalty, int32_t* gain, int32_t* accepted, int32_t* best_step,
                                  int32_t* kempe_stats, void* stream) {
-    int rc = check_pop_args(p, P, slot, room);
-    if (rc) return rc;
-    if (!rng) { set_error("tt_lahc_kempe_aug: null rng buffer"); return TT_ERR_INVALID; }
-    if (steps < 0) { set_error("tt_lahc_kempe_aug: negative steps"); return TT_ERR_INVALID; }
-    if (history < 1) { set_error("tt_lahc_kempe_aug: history must be at least 1"); return TT_ERR_INVALID; }
-    if (!(p_swap >= 0.0 && p_swap <= 1.0)) { set_error("tt_lahc_kempe_aug: p_swap outside [0, 1]"); return TT_ERR_INVALID; }
-    if (!(p_kempe >= 0.0 && p_kempe <= 1.0)) { set_error("tt_lahc_kempe_aug: p_kempe outside [0, 1]"); return TT_ERR_INVALID; }
-    if (max_chain < 0) { set_error("tt_lahc_kempe_aug: negative max_chain"); return TT_ERR_INVALID; }
-    if (room_rule != 0 && room_rule != 1) { set_error("tt_lahc_kempe_aug: room_rule must be 0 or 1"); return TT_ERR_INVALID; }
-    const double kempe_from = 1.0 - p_kempe;
-    if (!(p_swap <= kempe_from)) { set_error("tt_lahc_kempe_aug: p_swap above 1 - p_kempe"); return TT_ERR_INVALID; }
-    if (P == 0) return TT_OK;
-    const size_t lds = lahc_kempe_aug_lds_bytes(p->E, p->S, history);
-    if (lds > kLahcMaxLds || p->dev.EW64 > 64 * kLkLaneWords) {
-        set_error("instance or history too large for the late-acceptance search with augmenting Kempe chains");
-        return TT_ERR_LIMIT;
-    }
+    size_t lds = 0;
+    int rc = lahc_check_args("tt_lahc_kempe_aug", kLahcAug, p, P, slot, room, rng, steps, history, p_swap, p_kempe,
+                             max_chain, room_rule, &lds);
+    if (rc || P == 0) return rc;
     if ((rc = use_device(p))) return rc;
     hipLaunchKernelGGL(lahc_kempe_aug_kernel, dim3(P), dim3(64), lds, (hipStream_t)stream, p->dev, slot, room, rng, P,
-                       steps, history, p_swap, p_kempe, kempe_from, max_chain, room_rule, scv, penalty, gain, accepted,
-                       best_step, kempe_stats);
+                       steps, history, p_swap, p_kempe, 1.0 - p_kempe, max_chain, room_rule, scv, penalty, gain,
+                       accepted, best_step, kempe_stats);
     return check_hip(hipGetLastError(), "lahc_kempe_aug launch");
 }

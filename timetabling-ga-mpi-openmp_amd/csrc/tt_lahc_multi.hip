@@ -5,15 +5,15 @@
 // No counterpart in the reference; its call site is tt_lahc's.
 //
 // Two launches on the caller's stream. lahc_multi_walk_kernel: P * K waves, wave q is walker
-// q % K of row q / K, tt_lahc_kempe_walk.h's walk with kAug and kMulti. It reads the row and
-// rng[p] and writes nothing but its own part of `work` (and the status bit of a bad gene).
+// q % K of row q / K, tt_lahc_walk.h's lahc_chain_walk with kAug and kMulti. It reads the row
+// and rng[p] and writes nothing but its own part of `work` (and the status bit of a bad gene).
 // lahc_multi_commit_kernel, behind it: one wave per row takes the lowest-index maximum of
 // the K gains, copies the winner's row and numbers out of `work` and moves rng[p] on. The
 // stream orders the two, so a walker never sees a committed row and the commit sees every
 // walker's writes. With K = 1 the call is tt_lahc_kempe_aug itself (lahc_kempe_aug_kernel,
 // no work buffer) and a fill of winner and walker_gain.
 #include "../../include/ttga_lahc_multi.h"
-#include "tt_lahc_kempe_walk.h"
+#include "tt_lahc_walk.h"
 #include "tt_place.h"
 
 namespace ttga {
@@ -27,7 +27,7 @@ __global__ __launch_bounds__(64) void lahc_multi_walk_kernel(DevProblem pb, cons
                                                              double kempe_from, int max_chain, int room_rule,
                                                              void* __restrict__ work) {
     // the walk's pointers are not const: under kMulti it stores through none of them
-    lahc_kempe_walk<true, true>(pb, const_cast<uint8_t*>(slot), const_cast<uint8_t*>(room), const_cast<int64_t*>(rng),
+    lahc_chain_walk<true, true>(pb, const_cast<uint8_t*>(slot), const_cast<uint8_t*>(room), const_cast<int64_t*>(rng),
                                 P, steps, L, p_swap, p_kempe, kempe_from, max_chain, room_rule, nullptr, nullptr,
                                 nullptr, nullptr, nullptr, nullptr, walkers, work);
 }
@@ -89,11 +89,7 @@ __global__ __launch_bounds__(64) void lahc_multi_commit_kernel(int E, int P, int
         if (accepted) accepted[p] = src[kLmAccepted];
         if (best_step) best_step[p] = src[kLmBestStep];
         if (winner) winner[p] = win;
-        if (scv) scv[p] -= top;
-        if (penalty) {
-            const int pen = penalty[p];
-            if (pen >= 0 && pen < 1000000) penalty[p] = pen - top;
-        }
+        lahc_credit(scv, penalty, p, top);
     }
 }
 
@@ -121,28 +117,18 @@ extern "C" int tt_lahc_multi(const tt_problem* p, uint8_t* slot, uint8_t* room, 
                              int steps, int history, double p_swap, double p_kempe, int max_chain, int room_rule,
                              int32_t* scv, int32_t* penalty, int32_t* gain, int32_t* accepted, int32_t* best_step,
                              int32_t* kempe_stats, int32_t* winner, int32_t* walker_gain, void* work, void* stream) {
-    int rc = check_pop_args(p, P, slot, room);
+    const char* fn = "tt_lahc_multi";
+    int rc = lahc_check_rows(fn, p, P, slot, room, rng);
     if (rc) return rc;
-    if (!rng) { set_error("tt_lahc_multi: null rng buffer"); return TT_ERR_INVALID; }
     if (walkers < 1 || walkers > kLmMaxWalkers) { set_error("tt_lahc_multi: walkers outside 1 .. 1024"); return TT_ERR_INVALID; }
-    if (steps < 0) { set_error("tt_lahc_multi: negative steps"); return TT_ERR_INVALID; }
-    if (history < 1) { set_error("tt_lahc_multi: history must be at least 1"); return TT_ERR_INVALID; }
-    if (!(p_swap >= 0.0 && p_swap <= 1.0)) { set_error("tt_lahc_multi: p_swap outside [0, 1]"); return TT_ERR_INVALID; }
-    if (!(p_kempe >= 0.0 && p_kempe <= 1.0)) { set_error("tt_lahc_multi: p_kempe outside [0, 1]"); return TT_ERR_INVALID; }
-    if (max_chain < 0) { set_error("tt_lahc_multi: negative max_chain"); return TT_ERR_INVALID; }
-    if (room_rule != 0 && room_rule != 1) { set_error("tt_lahc_multi: room_rule must be 0 or 1"); return TT_ERR_INVALID; }
-    const double kempe_from = 1.0 - p_kempe;
-    if (!(p_swap <= kempe_from)) { set_error("tt_lahc_multi: p_swap above 1 - p_kempe"); return TT_ERR_INVALID; }
+    if ((rc = lahc_check_walk(fn, kLahcAug, steps, history, p_swap, p_kempe, max_chain, room_rule))) return rc;
     if (walkers > 1 && (!work || ((uintptr_t)work & 7u) != 0)) {
         set_error("tt_lahc_multi: work must be an 8-byte aligned buffer when walkers > 1");
         return TT_ERR_INVALID;
     }
     if (P == 0) return TT_OK;
-    const size_t lds = lahc_kempe_aug_lds_bytes(p->E, p->S, history);
-    if (lds > kLahcMaxLds || p->dev.EW64 > 64 * kLkLaneWords) {
-        set_error("instance or history too large for the late-acceptance search with augmenting Kempe chains");
-        return TT_ERR_LIMIT;
-    }
+    size_t lds = 0;
+    if ((rc = lahc_check_lds(kLahcAug, p, history, &lds))) return rc;
     if ((long long)P * walkers > (long long)INT_MAX) {
         set_error("tt_lahc_multi: P * walkers above 2^31 - 1");
         return TT_ERR_LIMIT;
@@ -161,8 +147,8 @@ extern "C" int tt_lahc_multi(const tt_problem* p, uint8_t* slot, uint8_t* room, 
     }
     if ((rc = use_device(p))) return rc;
     hipLaunchKernelGGL(lahc_multi_walk_kernel, dim3((unsigned)(P * walkers)), dim3(64), lds, (hipStream_t)stream, p->dev,
-                       slot, room, rng, P, walkers, steps, history, p_swap, p_kempe, kempe_from, max_chain, room_rule,
-                       work);
+                       slot, room, rng, P, walkers, steps, history, p_swap, p_kempe, 1.0 - p_kempe, max_chain,
+                       room_rule, work);
     if ((rc = check_hip(hipGetLastError(), "lahc_multi walk launch"))) return rc;
     hipLaunchKernelGGL(lahc_multi_commit_kernel, dim3(P), dim3(64), 0, (hipStream_t)stream, p->E, P, walkers, work, slot,
                        room, rng, scv, penalty, gain, accepted, best_step, kempe_stats, winner, walker_gain);

@@ -1,44 +1,403 @@
-// The late-acceptance walk with Kempe-chain candidates, shared by tt_lahc_kempe.hip
-// (kAug false: the rooms chosen directly, five counts) and tt_lahc_kempe_aug.hip (kAug
-// true: a room_rule argument, rooms by augmenting paths, seven counts). Everything the
-// new rule needs stands under `if constexpr (kAug)`, so lahc_kempe_kernel compiles to the
-// instructions and registers it had before the walk moved here.
+// The late-acceptance walk on feasible rows (include/ttga_lahc*.h), shared by tt_lahc.hip,
+// tt_lahc_kempe.hip, tt_lahc_kempe_aug.hip and tt_lahc_multi.hip: the LDS image and its one
+// carve, the pieces that lahc_kernel composes (entry, the walk's running state, the
+// acceptance rule and its bookkeeping, the plain step, the exits), the walk with chains
+// (lahc_chain_walk, one body for lahc_kempe_kernel, lahc_kempe_aug_kernel and
+// lahc_multi_walk_kernel), and the host's argument checks.
 //
-// tt_lahc.hip's header holds for the state and for Move1 / Move2, whose code here is
-// lahc_kernel's. A chain K on a feasible row: a student of an event of K attends one
-// event of the two slots, or one on each side, both of them in K. The first kind's mask
-// flips both slots' bits, the second kind's mask stays. A slot of a feasible row holds
-// at most R <= 64 events (one room each), so a chain has at most 128.
+// On a feasible row a student attends at most one event per slot, so scv is a sum over
+// the students of a function of the 45-bit attendance mask m: per 9-bit day,
+// [bit 8] + the windows of three set bits + [exactly one bit]. A move of event e from
+// slot a to slot t turns m into m ^ bit a ^ bit t for the students of e and for nobody
+// else, and only the days of a and t change their cost. The feasibility of a candidate
+// is one AND of the event's correlation row with the target slot's event bitset and
+// one AND of its possible rooms with the slot's free rooms; no matcher runs.
+//
+// One wave (workgroup) per walk. Everything that decides a step is wave-uniform: every
+// lane draws the same three numbers from its own copy of the state, and the words that
+// all lanes update (set and occ outside a chain, the two genes of Move1 / Move2, hist,
+// klist, koff, kroom) are written by every lane with the same value to the same address,
+// so each lane later reads what it wrote itself. What one lane writes and another reads
+// is named at the piece that writes it, with the barrier that covers it.
 #pragma once
 #include "../../include/ttga_lahc.h"
 #include "tt_internal.h"
-#include "tt_lahc_common.h"
 
 namespace ttga {
 
+constexpr int kStatusLahcBadGene = 256;     // tt_device_status bit 8
+constexpr size_t kLahcMaxLds = 64 * 1024;
 constexpr int kChainMax = 2 * kMaxRooms;    // the events of two slots of a feasible row
 // correlation-row words a lane accumulates (words l, l + 64): 128 words = 8,192 events;
 // the LDS formula admits no more than 101 words (47 bitset words and 256 gene bytes a word)
 constexpr int kLkLaneWords = 2;
-// klist[128] i32 | koff[128 + 4] i32 | kroom[128] u8
-constexpr size_t kLkFixedBytes = 4 * kChainMax + 4 * (kChainMax + 4) + kChainMax;
-
-// LDS of one wave: set[45][EW64] u64 | occ[45] u64 | K[EW64] u64 | F[EW64] u64 | mask[S] u64 |
-//                  hist[L] i32 | klist | koff | sl[E] | rr[E] | bsl[E] | brr[E] | kroom  (u8)
-__host__ __device__ inline size_t lahc_kempe_lds_bytes(int E, int S, int L) {
-    return 8 * ((size_t)(kSlots + 2) * (size_t)((E + 63) / 64) + kSlots + (size_t)S) + 4 * (size_t)L + 4 * (size_t)E +
-           kLkFixedBytes;
-}
-
-// the augmenting search's state behind kroom: hold[2][64] i16 (room -> event, -1: free; the
-// table of slot a, then of slot t) | qpar[64] u8 | queue[64] u8
-constexpr size_t kLkAugBytes = 2 * 2 * kMaxRooms + kMaxRooms + kMaxRooms;
 constexpr int kLkRoot = 0xFF;               // qpar of a room of poss[e]: the event itself takes it
 
-__host__ __device__ inline size_t lahc_kempe_aug_lds_bytes(int E, int S, int L) {
-    return lahc_kempe_lds_bytes(E, S, L) + kLkAugBytes;
+// ---- the LDS image
+// What a kernel's walk keeps in LDS: the plain walk, the walk with chains, or the walk
+// with chains and the augmenting search's tables.
+enum LahcKind { kLahcPlain, kLahcChain, kLahcAug };
+
+// set[45][EW64] u64 | occ[45] u64 | K[EW64] F[EW64] u64 (chains) | mask[S] u64 | hist[L] i32 |
+// klist[128] koff[128 + 4] i32 (chains) | sl[E] rr[E] bsl[E] brr[E] u8 | kroom[128] u8 (chains) |
+// hold[2][64] i16 (room -> event, -1: free; the table of slot a, then of slot t), qpar[64]
+// queue[64] u8 (augment). A pointer the kind does not have is null.
+struct LahcLds {
+    uint64_t *set, *occ, *K, *F, *mask;
+    int32_t *hist, *klist, *koff;
+    uint8_t *sl, *rr, *bsl, *brr, *kroom;
+    int16_t* hold;
+    uint8_t *qpar, *queue;
+    size_t bytes;                           // of the whole image
+};
+
+// the next n elements of type T: counted in `off`, and in a kernel taken at `base`, which
+// moves on; the host and the compiler only count
+template <class T>
+__host__ __device__ constexpr T* lahc_take(uint8_t*& base, size_t& off, size_t n) {
+    off += n * sizeof(T);
+#ifdef __HIP_DEVICE_COMPILE__
+    if (!__builtin_is_constant_evaluated()) {
+        T* at = (T*)base;
+        base = (uint8_t*)(at + n);
+        return at;
+    }
+#endif
+    return nullptr;
 }
 
+// The one carve: a kernel calls it with its LDS, the host with a null base for `bytes`.
+__host__ __device__ constexpr LahcLds lahc_carve(LahcKind kind, uint8_t* base, int E, int EW64, int S, int L) {
+    LahcLds m{};
+    size_t off = 0;
+    m.set = lahc_take<uint64_t>(base, off, (size_t)kSlots * EW64);
+    m.occ = lahc_take<uint64_t>(base, off, kSlots);
+    if (kind != kLahcPlain) {
+        m.K = lahc_take<uint64_t>(base, off, EW64);
+        m.F = lahc_take<uint64_t>(base, off, EW64);
+    }
+    m.mask = lahc_take<uint64_t>(base, off, S);
+    m.hist = lahc_take<int32_t>(base, off, L);
+    if (kind != kLahcPlain) {
+        m.klist = lahc_take<int32_t>(base, off, kChainMax);
+        m.koff = lahc_take<int32_t>(base, off, kChainMax + 4);
+    }
+    m.sl = lahc_take<uint8_t>(base, off, E);
+    m.rr = lahc_take<uint8_t>(base, off, E);
+    m.bsl = lahc_take<uint8_t>(base, off, E);
+    m.brr = lahc_take<uint8_t>(base, off, E);
+    if (kind != kLahcPlain) m.kroom = lahc_take<uint8_t>(base, off, kChainMax);
+    if (kind == kLahcAug) {
+        m.hold = lahc_take<int16_t>(base, off, 2 * kMaxRooms);
+        m.qpar = lahc_take<uint8_t>(base, off, kMaxRooms);
+        m.queue = lahc_take<uint8_t>(base, off, kMaxRooms);
+    }
+    m.bytes = off;
+    return m;
+}
+
+__host__ __device__ constexpr size_t lahc_lds_bytes(LahcKind kind, int E, int S, int L) {
+    return lahc_carve(kind, nullptr, E, (E + 63) / 64, S, L).bytes;
+}
+
+// the limits that include/ttga_lahc*.h document: 8 (45 EW64 + 45 + S) + 4 L + 4 E plain;
+// 8 (47 EW64 + 45 + S) + 4 L + 4 E + 1,168 with chains; 384 more with the tables
+static_assert(lahc_lds_bytes(kLahcPlain, 100, 80, 0) == 2120, "sm without the history");
+static_assert(lahc_lds_bytes(kLahcChain, 400, 200, 500) == 9360, "med with chains");
+static_assert(lahc_lds_bytes(kLahcChain, 2000, 5000, 100) == 61960, "syn with chains");
+static_assert(lahc_lds_bytes(kLahcAug, 400, 200, 500) == 9360 + 384, "med with the tables");
+static_assert(lahc_lds_bytes(kLahcAug, 2000, 5000, 100) == 61960 + 384, "syn with the tables");
+
+// ---- small helpers
+// one day's cost of a student: last slot of the day, windows of three, single class
+__device__ __forceinline__ int lahc_day_cost(uint64_t m, int day) {
+    const uint32_t d = (uint32_t)(m >> (9 * day)) & 0x1FFu;
+    return (int)(d >> 8) + __popc(d & (d >> 1) & (d >> 2)) + (__popc(d) == 1);
+}
+
+// cost(m ^ flip) - cost(m) where flip has bits on days da and db only
+__device__ __forceinline__ int lahc_mask_delta(uint64_t m, uint64_t flip, int da, int db) {
+    const uint64_t n = m ^ flip;
+    int d = lahc_day_cost(n, da) - lahc_day_cost(m, da);
+    if (db != da) d += lahc_day_cost(n, db) - lahc_day_cost(m, db);
+    return d;
+}
+
+__device__ __forceinline__ int lahc_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+// lane r's 64-bit value, r the same in every lane
+__device__ __forceinline__ uint64_t lahc_lane64(uint64_t v, int r) {
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), r) << 32) |
+           (uint32_t)__builtin_amdgcn_readlane((int)v, r);
+}
+
+// what a finished walk does to the row's scv and penalty: the penalty of a feasible row is
+// its scv, anything else (an infeasible row's 1000000 + hcv) stays
+__device__ __forceinline__ void lahc_credit(int32_t* scv, int32_t* penalty, long p, int g) {
+    if (scv) scv[p] -= g;
+    if (penalty) {
+        const int pen = penalty[p];
+        if (pen >= 0 && pen < 1000000) penalty[p] = pen - g;
+    }
+}
+
+// ---- entry: the row, validity, the bitsets, the student masks and the hcv gate
+struct LahcEntry {
+    bool closed;                            // the row does not walk: a bad gene, hcv > 0 or steps == 0
+    bool bad_gene;                          // a gene out of range: nothing but sl / rr was built
+};
+
+// Lane roles: event per lane (genes, bitsets), then student per lane (masks). set and occ
+// are built with LDS atomics; the barrier at the end covers them, the masks and hist, so
+// the walk starts on an image every lane sees. What a closed row writes is the caller's exit.
+// Loop bounds: ceil(E / 64) events, ceil((45 EW64 + 45) / 64) words, ceil(L / 64) history
+// entries and ceil(S / 64) students per lane, each student over its own events.
+__device__ __forceinline__ LahcEntry lahc_enter(const DevProblem& pb, const LahcLds& lds, const uint8_t* slot,
+                                                const uint8_t* room, long p, int steps, int L, int lane) {
+    const int E = pb.E, R = pb.R, S = pb.S, EW64 = pb.EW64;
+    bool bad = false;
+    for (int e = lane; e < E; e += 64) {
+        const uint8_t s = slot[p * E + e], r = room[p * E + e];
+        lds.sl[e] = s;
+        lds.rr[e] = r;
+        bad |= s >= kSlots || r >= R;
+    }
+    for (int i = lane; i < kSlots * EW64 + kSlots; i += 64) lds.set[i] = 0ull;    // set and occ are adjacent
+    for (int i = lane; i < L; i += 64) lds.hist[i] = 0;                           // costs are kept relative to scv0
+    __syncthreads();
+    const bool bad_row = wave_any(bad);
+    bool hard = false;                                  // a hard-constraint violation seen by this lane
+    if (!bad_row) {
+        for (int e = lane; e < E; e += 64) {
+            const int s = lds.sl[e], r = lds.rr[e];
+            atomicOr((unsigned long long*)&lds.set[(size_t)s * EW64 + (e >> 6)], 1ull << (e & 63));
+            const unsigned long long old = atomicOr((unsigned long long*)&lds.occ[s], 1ull << r);
+            hard |= ((old >> r) & 1ull) != 0ull;            // two events in one room of one slot
+            hard |= ((pb.poss[e] >> r) & 1ull) == 0ull;     // a room that is not possible
+        }
+        // two correlated events share a student: they are in one slot exactly if some
+        // student's events cover fewer slots than the student has events
+        for (int s = lane; s < S; s += 64) {
+            const int b = pb.stu_off[s], end = pb.stu_off[s + 1];
+            uint64_t m = 0ull;
+            for (int i = b; i < end; ++i) m |= 1ull << lds.sl[pb.stu_ev[i]];
+            lds.mask[s] = m;
+            hard |= __popcll(m) != end - b;
+        }
+        __syncthreads();
+    }
+    return {bad_row || wave_any(hard) || steps == 0, bad_row};
+}
+
+// ---- the walk's running state; cur and best are relative to the row's scv at entry
+struct LahcWalk {
+    int64_t st;                             // the stream
+    int cur = 0, best = 0, n_acc = 0, b_step = 0;
+    bool live_is_best = true;               // the best row is the row in sl / rr
+    int v = 0;                              // the history entry this step reads and writes
+};
+
+// A step's three draws, the same in every lane: the event, Move1 or Move2, and the number x
+// that picks the second slot or event.
+struct LahcDraw {
+    int e1, a;                              // the event and its slot
+    double x;
+    bool swap;
+};
+__device__ __forceinline__ LahcDraw lahc_draw(const DevProblem& pb, const LahcLds& m, LahcWalk& w, double p_swap) {
+    const int E = pb.E;
+    LahcDraw c;
+    c.e1 = min(max(lahc_uniform(pm_pick(w.st, E)), 0), E - 1);
+    const double u = pm_next(w.st);
+    c.x = pm_next(w.st);
+    c.swap = E >= 2 && lahc_uniform((int)(u < p_swap)) != 0;
+    c.a = lahc_uniform((int)m.sl[c.e1]);
+    return c;
+}
+
+// the second slot of Move1: one of the 44 others
+__device__ __forceinline__ int lahc_other_slot(double x, int a) {
+    int b = lahc_uniform((int)__dmul_rn(x, (double)(kSlots - 1)));
+    b += b >= a;
+    return min(max(b, 0), kSlots - 1);
+}
+
+// ---- the acceptance rule and its bookkeeping, for the plain step and the chain step alike
+__device__ __forceinline__ bool lahc_accepts(const LahcLds& m, const LahcWalk& w, int cand) {
+    return cand <= w.cur || cand <= lahc_uniform(m.hist[w.v]);
+}
+
+// Before an accepted candidate is applied: if the row in sl / rr is the best one and is
+// about to get worse (or stay level), it goes to bsl / brr. Lane = event; the barrier
+// stands between these reads of sl / rr and the writes of the move that follows, which
+// other lanes make (the chain's genes) or every lane makes (Move1 / Move2). ceil(E / 64)
+// events per lane.
+__device__ __forceinline__ void lahc_leave_best(const LahcLds& m, LahcWalk& w, int cand, int E, int lane) {
+    const bool leaves = w.live_is_best && cand >= w.cur;
+    if (leaves) {
+        for (int e = lane; e < E; e += 64) { m.bsl[e] = m.sl[e]; m.brr[e] = m.rr[e]; }
+        __syncthreads();
+    }
+    w.live_is_best = w.live_is_best && !leaves;
+}
+
+// after step k's candidate is applied
+__device__ __forceinline__ void lahc_accepted(LahcWalk& w, int cand, int k) {
+    const bool better = cand < w.best;
+    w.cur = cand;
+    ++w.n_acc;
+    if (better) {
+        w.best = cand;
+        w.b_step = k + 1;
+    }
+    w.live_is_best = w.live_is_best || better;
+}
+
+// the end of every step, accepted or not; every lane writes the one entry
+__device__ __forceinline__ void lahc_remember(const LahcLds& m, LahcWalk& w, int L) {
+    m.hist[w.v] = w.cur;
+    w.v = w.v + 1 == L ? 0 : w.v + 1;
+}
+
+// ---- the plain step: Move1 (e1 to another slot) or Move2 (e1 and e2 trade slots)
+// Lane roles: correlation test = bitset word per lane; delta and apply = student of the
+// moved event(s) per lane. The bitsets, occ and the one or two genes are written by every
+// lane alike; the student masks are written by one lane and read by another: the barrier
+// at the end of an applied move covers them.
+// Loop bounds: ceil(EW64 / 64) words and ceil(students of the one or two events / 64)
+// students per lane.
+__device__ __forceinline__ void lahc_plain_step(const DevProblem& pb, const LahcLds& m, LahcWalk& wk,
+                                                const LahcDraw& c, int k, int lane) {
+    const int E = pb.E, EW64 = pb.EW64, e1 = c.e1, a = c.a;
+    const bool swap = c.swap;
+    const int off1 = pb.ev_off[e1], n1 = pb.ev_off[e1 + 1] - off1;
+    int e2 = e1, b, r1, r2 = 0, off2 = 0, n2 = 0;
+    bool feas;
+    if (swap) {
+        e2 = lahc_uniform((int)__dmul_rn(c.x, (double)(E - 1)));
+        e2 += e2 >= e1;
+        e2 = min(max(e2, 0), E - 1);
+        b = lahc_uniform((int)m.sl[e2]);
+        off2 = pb.ev_off[e2];
+        n2 = pb.ev_off[e2 + 1] - off2;
+        bool clash = false;
+        for (int w = lane; w < EW64; w += 64) {
+            uint64_t sb = m.set[(size_t)b * EW64 + w], sa = m.set[(size_t)a * EW64 + w];
+            if (w == (e2 >> 6)) sb &= ~(1ull << (e2 & 63));
+            if (w == (e1 >> 6)) sa &= ~(1ull << (e1 & 63));
+            clash |= ((pb.corr64[(size_t)e1 * EW64 + w] & sb) | (pb.corr64[(size_t)e2 * EW64 + w] & sa)) != 0ull;
+        }
+        const uint64_t f1 = pb.poss[e1] & ~(m.occ[b] & ~(1ull << m.rr[e2]));
+        const uint64_t f2 = pb.poss[e2] & ~(m.occ[a] & ~(1ull << m.rr[e1]));
+        r1 = lahc_uniform(__ffsll((unsigned long long)f1) - 1);
+        r2 = lahc_uniform(__ffsll((unsigned long long)f2) - 1);
+        feas = a != b && r1 >= 0 && r2 >= 0 && !wave_any(clash);
+    } else {
+        b = lahc_other_slot(c.x, a);
+        bool clash = false;
+        for (int w = lane; w < EW64; w += 64)
+            clash |= (pb.corr64[(size_t)e1 * EW64 + w] & m.set[(size_t)b * EW64 + w]) != 0ull;
+        const uint64_t f1 = pb.poss[e1] & ~m.occ[b];
+        r1 = lahc_uniform(__ffsll((unsigned long long)f1) - 1);
+        feas = r1 >= 0 && !wave_any(clash);
+    }
+    if (!feas) return;
+    // the students of e1, then (Move2) of e2; one who attends both keeps the mask:
+    // the other slot's bit is set for nobody else, the candidate being feasible
+    const uint64_t flip = (1ull << a) | (1ull << b);
+    const int da = a / kSlotsPerDay, db = b / kSlotsPerDay, n = n1 + n2;
+    int d = 0;
+    for (int i = lane; i < n; i += 64) {
+        const bool first = i < n1;
+        const uint64_t mm = m.mask[pb.ev_stu[first ? off1 + i : off2 + i - n1]];
+        if (!swap || ((mm >> (first ? b : a)) & 1ull) == 0ull) d += lahc_mask_delta(mm, flip, da, db);
+    }
+    const int cand = wk.cur + wave_sum(d);
+    if (!lahc_accepts(m, wk, cand)) return;
+    lahc_leave_best(m, wk, cand, E, lane);
+    for (int i = lane; i < n; i += 64) {
+        const bool first = i < n1;
+        const int s = pb.ev_stu[first ? off1 + i : off2 + i - n1];
+        const uint64_t mm = m.mask[s];
+        if (!swap || ((mm >> (first ? b : a)) & 1ull) == 0ull) m.mask[s] = mm ^ flip;
+    }
+    const uint64_t bit1 = 1ull << (e1 & 63);
+    uint64_t* wa1 = &m.set[(size_t)a * EW64 + (e1 >> 6)];
+    uint64_t* wb1 = &m.set[(size_t)b * EW64 + (e1 >> 6)];
+    *wa1 &= ~bit1;
+    *wb1 |= bit1;
+    const int ro1 = m.rr[e1];
+    if (swap) {
+        const uint64_t bit2 = 1ull << (e2 & 63);
+        uint64_t* wb2 = &m.set[(size_t)b * EW64 + (e2 >> 6)];
+        uint64_t* wa2 = &m.set[(size_t)a * EW64 + (e2 >> 6)];
+        *wb2 &= ~bit2;
+        *wa2 |= bit2;
+        const int ro2 = m.rr[e2];
+        m.occ[a] = (m.occ[a] & ~(1ull << ro1)) | (1ull << r2);
+        m.occ[b] = (m.occ[b] & ~(1ull << ro2)) | (1ull << r1);
+        m.sl[e2] = (uint8_t)a;
+        m.rr[e2] = (uint8_t)r2;
+    } else {
+        m.occ[a] &= ~(1ull << ro1);
+        m.occ[b] |= 1ull << r1;
+    }
+    m.sl[e1] = (uint8_t)b;
+    m.rr[e1] = (uint8_t)r1;
+    lahc_accepted(wk, cand, k);
+    __syncthreads();                        // the masks: written by one lane, read by another
+}
+
+// ---- the single-row exits
+// the optional per-row outputs of the three single-walk entry points; kstats: n_stats a row
+struct LahcOut {
+    int32_t *scv, *penalty, *gain, *accepted, *best_step, *kstats;
+};
+
+// a row that did not walk: zeros, and the status bit of a bad gene
+__device__ __forceinline__ void lahc_exit_closed(const DevProblem& pb, const LahcOut& o, int n_stats, long p,
+                                                 LahcEntry in, int lane) {
+    if (lane == 0) {
+        if (o.gain) o.gain[p] = 0;
+        if (o.accepted) o.accepted[p] = 0;
+        if (o.best_step) o.best_step[p] = 0;
+        if (in.bad_gene) atomicOr(pb.status, kStatusLahcBadGene);
+    }
+    if (o.kstats && lane < n_stats) o.kstats[p * n_stats + lane] = 0;
+}
+
+// The best row seen goes back if a step improved on the entry row (lane = event,
+// ceil(E / 64) per lane; the last applied move's barrier covers sl / rr, lahc_leave_best's
+// bsl / brr); lane 0 writes the stream and the row's numbers.
+__device__ __forceinline__ void lahc_exit_row(const LahcLds& m, const LahcWalk& w, const LahcOut& o, uint8_t* slot,
+                                              uint8_t* room, int64_t* rng, long p, int E, int lane) {
+    if (w.b_step > 0) {
+        const uint8_t* os = w.live_is_best ? m.sl : m.bsl;
+        const uint8_t* orr = w.live_is_best ? m.rr : m.brr;
+        for (int e = lane; e < E; e += 64) {
+            slot[p * E + e] = os[e];
+            room[p * E + e] = orr[e];
+        }
+    }
+    if (lane == 0) {
+        rng[p] = w.st;
+        const int g = -w.best;
+        if (o.gain) o.gain[p] = g;
+        if (o.accepted) o.accepted[p] = w.n_acc;
+        if (o.best_step) o.best_step[p] = w.b_step;
+        lahc_credit(o.scv, o.penalty, p, g);
+    }
+}
+
+// ---- the walk with chains
+// One body, as it was before lahc_kernel was taken apart into the pieces above. The three
+// kernels it serves are held to the instructions they had, and they lose them as soon as
+// the body calls one of those pieces (the entry, the plain step, the acceptance helpers, the
+// row exit, even the carve: each was tried, and each moves at least a few instructions). So
+// the body keeps its own pointer chain over the LDS image, in lahc_carve's order, its own
+// entry and its own Move1 / Move2 path, which are lahc_enter's and lahc_plain_step's line for
+// line; a change to one is made to the other. Of the pieces it shares lahc_exit_closed.
+//
 // tt_lahc_multi's work buffer for P rows of K walkers, wave q = row * K + walker:
 //   state[P] i64      the row's stream state behind all K walks (the last walker writes it)
 //   nums[P K][12] i32 walker q's gain, accepted, best_step, the seven counts, walked (0: the
@@ -70,20 +429,8 @@ __device__ __forceinline__ int64_t lahc_multi_start(int64_t s, int steps, int w)
     return s;
 }
 
-// a 64-bit value every lane holds alike, as a scalar
-__device__ __forceinline__ uint64_t lahc_uniform64(uint64_t v) {
-    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
-           (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-}
-
-// lane r's 64-bit value, r the same in every lane
-__device__ __forceinline__ uint64_t lahc_lane64(uint64_t v, int r) {
-    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), r) << 32) |
-           (uint32_t)__builtin_amdgcn_readlane((int)v, r);
-}
-
-// One wave (workgroup) per individual; lahc_kernel's rules on who writes what hold for
-// Move1 and Move2. A Kempe candidate adds words that one lane writes and another reads:
+// One wave (workgroup) per individual; the rules of lahc_enter and lahc_plain_step on who
+// writes what hold for the entry and for Move1 and Move2. A Kempe candidate adds words that one lane writes and another reads:
 // K and F during the component search (a barrier after every round's reads and after
 // every round's writes, as kempe_kernel), and on an applied chain the two slots' event
 // bitsets (lane = word), the genes of the chain's events (lane = event of K) and the
@@ -115,7 +462,7 @@ __device__ __forceinline__ uint64_t lahc_lane64(uint64_t v, int r) {
 // needs stands under `if constexpr (kMulti)`, so the other kernels compile to the
 // instructions they had.
 template <bool kAug, bool kMulti = false>
-__device__ __forceinline__ void lahc_kempe_walk(const DevProblem& pb, uint8_t* __restrict__ slot,
+__device__ __forceinline__ void lahc_chain_walk(const DevProblem& pb, uint8_t* __restrict__ slot,
                                                 uint8_t* __restrict__ room, int64_t* __restrict__ rng, int P, int steps,
                                                 int L, double p_swap, double p_kempe, double kempe_from, int max_chain,
                                                 int room_rule, int32_t* __restrict__ scv, int32_t* __restrict__ penalty,
@@ -177,20 +524,14 @@ __device__ __forceinline__ void lahc_kempe_walk(const DevProblem& pb, uint8_t* _
         }
         __syncthreads();
     }
-    if (bad_row || wave_any(hard) || steps == 0) {
+    const LahcEntry in{bad_row || wave_any(hard) || steps == 0, bad_row};
+    if (in.closed) {
         if constexpr (kMulti) {                         // a closed row: zeros, the flag among them
             if (lane < kLmNums) lahc_multi_work(work, P, walkers, E).nums[q * kLmNums + lane] = 0;
-            if (bad_row && lane == 0) atomicOr(pb.status, kStatusLahcBadGene);
+            if (in.bad_gene && lane == 0) atomicOr(pb.status, kStatusLahcBadGene);
             return;
         }
-        if (lane == 0) {
-            if (gain) gain[p] = 0;
-            if (accepted) accepted[p] = 0;
-            if (best_step) best_step[p] = 0;
-            if (bad_row) atomicOr(pb.status, kStatusLahcBadGene);
-        }
-        if (kstats && lane < kStats) kstats[p * kStats + lane] = 0;
-        return;
+        return lahc_exit_closed(pb, {scv, penalty, gain, accepted, best_step, kstats}, kStats, p, in, lane);
     }
 
     // ---- the walk (cur and best relative to scv0)
@@ -224,7 +565,7 @@ __device__ __forceinline__ void lahc_kempe_walk(const DevProblem& pb, uint8_t* _
 #pragma unroll
                 for (int j = 0; j < kLkLaneWords; ++j) acc[j] = 0ull;
                 for (int fw = 0; fw < EW64; ++fw) {
-                    uint64_t xw = lahc_uniform64(F[fw]);        // one address for the wave
+                    uint64_t xw = wave_uniform64(F[fw]);        // one address for the wave
                     for (int g = 0; g < 64 && xw; ++g) {
                         const int f = 64 * fw + (__ffsll((unsigned long long)xw) - 1);
                         xw &= xw - 1;
@@ -265,14 +606,14 @@ __device__ __forceinline__ void lahc_kempe_walk(const DevProblem& pb, uint8_t* _
             }
             // ---- the rooms: the chain leaves its own, then takes new ones in ascending order
             uint64_t oa = occ[a], ob = occ[b];
-            oa = lahc_uniform64(oa);
-            ob = lahc_uniform64(ob);
+            oa = wave_uniform64(oa);
+            ob = wave_uniform64(ob);
             int n = 0, pairs = 0;
             [[maybe_unused]] bool built = false, augmented = false;     // the holder tables stand; a path was used
             [[maybe_unused]] uint64_t pwa = 0ull, pwb = 0ull;           // lane r: poss of the holder of room r in a, in t
             if (feas) {
                 for (int w = 0; w < EW64; ++w) {
-                    uint64_t xw = lahc_uniform64(K[w]);
+                    uint64_t xw = wave_uniform64(K[w]);
                     for (int g = 0; g < 64 && xw && n < kChainMax; ++g) {
                         const int e = 64 * w + (__ffsll((unsigned long long)xw) - 1);
                         xw &= xw - 1;
@@ -289,7 +630,7 @@ __device__ __forceinline__ void lahc_kempe_walk(const DevProblem& pb, uint8_t* _
                     for (int i = 0; i < n; ++i) {
                         const int e = klist[i];
                         const bool to_b = lahc_uniform((int)sl[e]) == a;
-                        const uint64_t f = lahc_uniform64(pb.poss[e] & ~(to_b ? ob : oa));
+                        const uint64_t f = wave_uniform64(pb.poss[e] & ~(to_b ? ob : oa));
                         if (f == 0ull) { feas = false; break; }
                         const int r = __ffsll((unsigned long long)f) - 1;
                         if (to_b) ob |= 1ull << r; else oa |= 1ull << r;
@@ -299,7 +640,7 @@ __device__ __forceinline__ void lahc_kempe_walk(const DevProblem& pb, uint8_t* _
                     for (int i = 0; i < n; ++i) {
                         const int e = klist[i];
                         const bool to_b = lahc_uniform((int)sl[e]) == a;
-                        const uint64_t pe = lahc_uniform64(pb.poss[e]);
+                        const uint64_t pe = wave_uniform64(pb.poss[e]);
                         const uint64_t oc = to_b ? ob : oa;
                         int16_t* hd = hold + (to_b ? kMaxRooms : 0);        // the target slot's table
                         int r;
@@ -619,6 +960,59 @@ __device__ __forceinline__ void lahc_kempe_walk(const DevProblem& pb, uint8_t* _
             }
         }
     }
+}
+
+// ---- the host's argument checks, shared by tt_lahc, tt_lahc_kempe, tt_lahc_kempe_aug and
+// tt_lahc_multi (`fn`: the name in the messages), in three stages in the order the entry
+// points have always made them; tt_lahc_multi makes its own checks between the stages.
+// `kind` says which arguments the entry point has: p_kempe and max_chain come with the
+// chains, room_rule with the tables.
+
+// the population and the streams
+inline int lahc_check_rows(const std::string& fn, const tt_problem* p, int P, const uint8_t* slot,
+                           const uint8_t* room, const int64_t* rng) {
+    const int rc = check_pop_args(p, P, slot, room);
+    if (rc) return rc;
+    if (!rng) { set_error(fn + ": null rng buffer"); return TT_ERR_INVALID; }
+    return TT_OK;
+}
+
+// the walk's parameters
+inline int lahc_check_walk(const std::string& fn, LahcKind kind, int steps, int history, double p_swap, double p_kempe,
+                           int max_chain, int room_rule) {
+    if (steps < 0) { set_error(fn + ": negative steps"); return TT_ERR_INVALID; }
+    if (history < 1) { set_error(fn + ": history must be at least 1"); return TT_ERR_INVALID; }
+    if (!(p_swap >= 0.0 && p_swap <= 1.0)) { set_error(fn + ": p_swap outside [0, 1]"); return TT_ERR_INVALID; }
+    if (kind == kLahcPlain) return TT_OK;
+    if (!(p_kempe >= 0.0 && p_kempe <= 1.0)) { set_error(fn + ": p_kempe outside [0, 1]"); return TT_ERR_INVALID; }
+    if (max_chain < 0) { set_error(fn + ": negative max_chain"); return TT_ERR_INVALID; }
+    if (kind == kLahcAug && room_rule != 0 && room_rule != 1) {
+        set_error(fn + ": room_rule must be 0 or 1");
+        return TT_ERR_INVALID;
+    }
+    if (!(p_swap <= 1.0 - p_kempe)) { set_error(fn + ": p_swap above 1 - p_kempe"); return TT_ERR_INVALID; }
+    return TT_OK;
+}
+
+// the launch's LDS size into *lds, within the limit; made for P > 0 only
+inline int lahc_check_lds(LahcKind kind, const tt_problem* p, int history, size_t* lds) {
+    *lds = lahc_lds_bytes(kind, p->E, p->S, history);
+    if (*lds > kLahcMaxLds || (kind != kLahcPlain && p->dev.EW64 > 64 * kLkLaneWords)) {
+        const char* with[] = {"", " with Kempe chains", " with augmenting Kempe chains"};
+        set_error(std::string("instance or history too large for the late-acceptance search") + with[kind]);
+        return TT_ERR_LIMIT;
+    }
+    return TT_OK;
+}
+
+// the three stages of a single walk's entry point; TT_OK with P == 0 means there is nothing to do
+inline int lahc_check_args(const char* fn, LahcKind kind, const tt_problem* p, int P, const uint8_t* slot,
+                           const uint8_t* room, const int64_t* rng, int steps, int history, double p_swap,
+                           double p_kempe, int max_chain, int room_rule, size_t* lds) {
+    int rc = lahc_check_rows(fn, p, P, slot, room, rng);
+    if (!rc) rc = lahc_check_walk(fn, kind, steps, history, p_swap, p_kempe, max_chain, room_rule);
+    if (rc || P == 0) return rc;
+    return lahc_check_lds(kind, p, history, lds);
 }
 
 }  // namespace ttga

@@ -161,6 +161,19 @@ def _np_ptr(a: np.ndarray):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _ptr(t):
+    """The address of an optional tensor: NULL for None."""
+    return ctypes.c_void_p(t.data_ptr() if t is not None else None)
+
+
+def _opt_i32(name, t, n, what, device):
+    """An optional int32 output of n entries (`what` in words) on the population's device."""
+    import torch
+    if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n
+                              and t.device == device):
+        raise ValueError(f"{name} must be a contiguous int32 CUDA tensor of {what} entries on the population's device")
+
+
 class DeviceProblem:
     """A tt_problem handle: the Problem image resident on one GPU."""
 
@@ -478,16 +491,12 @@ class DeviceProblem:
         one event between two timeslots (at most max_chain events; 0: no cap).
         chain_len: optional int32 [P] CUDA tensor (events moved, minus the
         component's size where the cap refused it, 0 where nothing was tried)."""
-        import torch
         P = self._pop(slot, room)
         self._rng(rng, P)
-        if chain_len is not None and not (chain_len.is_cuda and chain_len.dtype == torch.int32
-                                          and chain_len.is_contiguous() and chain_len.numel() == P
-                                          and chain_len.device == slot.device):
-            raise ValueError("chain_len must be a contiguous int32 CUDA tensor of P entries on the population's device")
+        _opt_i32("chain_len", chain_len, P, "P", slot.device)
         _check(self.lib, self.lib.tt_kempe_move(
             self.handle, slot.data_ptr(), room.data_ptr(), rng.data_ptr(), P, float(prob), int(max_chain),
-            ctypes.c_void_p(chain_len.data_ptr() if chain_len is not None else None), self._stream(slot)))
+            _ptr(chain_len), self._stream(slot)))
 
     # -- timeslot-swap descent (include/ttga_slotswap.h) ------------------------------
     def slot_swap(self, slot, max_passes, scv=None, penalty=None, gain=None, passes=None, perm=None):
@@ -499,15 +508,13 @@ class DeviceProblem:
         import torch
         P = self._pop(slot)
         for name, t in (("scv", scv), ("penalty", penalty), ("gain", gain), ("passes", passes)):
-            if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == P
-                                      and t.device == slot.device):
-                raise ValueError(f"{name} must be a contiguous int32 CUDA tensor of P entries on the population's device")
+            _opt_i32(name, t, P, "P", slot.device)
         if perm is not None and not (perm.is_cuda and perm.dtype == torch.uint8 and perm.is_contiguous()
                                      and tuple(perm.shape) == (P, NUM_SLOTS) and perm.device == slot.device):
             raise ValueError("perm must be a contiguous uint8 CUDA tensor of shape [P, 45] on the population's device")
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)    # noqa: E731
-        _check(self.lib, self.lib.tt_slot_swap(self.handle, slot.data_ptr(), P, int(max_passes), ptr(scv), ptr(penalty),
-                                               ptr(gain), ptr(passes), ptr(perm), self._stream(slot)))
+        _check(self.lib, self.lib.tt_slot_swap(self.handle, slot.data_ptr(), P, int(max_passes), _ptr(scv),
+                                               _ptr(penalty), _ptr(gain), _ptr(passes), _ptr(perm),
+                                               self._stream(slot)))
 
     # -- late-acceptance search on feasible rows (include/ttga_lahc.h) -----------------
     def lahc(self, slot, room, rng, steps, history, p_swap=0.5, scv=None, penalty=None, gain=None, accepted=None,
@@ -517,18 +524,14 @@ class DeviceProblem:
         no worse than the current row or the one `history` steps ago; the best
         row seen comes back. scv, penalty (int32 [P], updated in place), gain,
         accepted and best_step (int32 [P]) are optional CUDA tensors."""
-        import torch
         P = self._pop(slot, room)
         self._rng(rng, P)
         for name, t in (("scv", scv), ("penalty", penalty), ("gain", gain), ("accepted", accepted),
                         ("best_step", best_step)):
-            if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == P
-                                      and t.device == slot.device):
-                raise ValueError(f"{name} must be a contiguous int32 CUDA tensor of P entries on the population's device")
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)    # noqa: E731
+            _opt_i32(name, t, P, "P", slot.device)
         _check(self.lib, self.lib.tt_lahc(self.handle, slot.data_ptr(), room.data_ptr(), rng.data_ptr(), P, int(steps),
-                                          int(history), float(p_swap), ptr(scv), ptr(penalty), ptr(gain),
-                                          ptr(accepted), ptr(best_step), self._stream(slot)))
+                                          int(history), float(p_swap), _ptr(scv), _ptr(penalty), _ptr(gain),
+                                          _ptr(accepted), _ptr(best_step), self._stream(slot)))
 
     def lahc_kempe(self, slot, room, rng, steps, history, p_swap=0.25, p_kempe=0.5, max_chain=0, scv=None, penalty=None,
                    gain=None, accepted=None, best_step=None, kempe_stats=None):
@@ -538,20 +541,16 @@ class DeviceProblem:
         with its rooms chosen directly; p_swap + p_kempe <= 1. The optional
         tensors are lahc()'s, and kempe_stats (int32 [P, 5]: chains tried,
         capped, without a room, accepted, and the events of the accepted ones)."""
-        import torch
         P = self._pop(slot, room)
         self._rng(rng, P)
-        for name, t, n in (("scv", scv, P), ("penalty", penalty, P), ("gain", gain, P), ("accepted", accepted, P),
-                           ("best_step", best_step, P), ("kempe_stats", kempe_stats, 5 * P)):
-            if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n
-                                      and t.device == slot.device):
-                raise ValueError(f"{name} must be a contiguous int32 CUDA tensor of {'5 P' if n != P else 'P'} entries "
-                                 "on the population's device")
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)    # noqa: E731
+        for name, t in (("scv", scv), ("penalty", penalty), ("gain", gain), ("accepted", accepted),
+                        ("best_step", best_step)):
+            _opt_i32(name, t, P, "P", slot.device)
+        _opt_i32("kempe_stats", kempe_stats, 5 * P, "5 P" if P else "P", slot.device)
         _check(self.lib, self.lib.tt_lahc_kempe(self.handle, slot.data_ptr(), room.data_ptr(), rng.data_ptr(), P,
                                                 int(steps), int(history), float(p_swap), float(p_kempe), int(max_chain),
-                                                ptr(scv), ptr(penalty), ptr(gain), ptr(accepted), ptr(best_step),
-                                                ptr(kempe_stats), self._stream(slot)))
+                                                _ptr(scv), _ptr(penalty), _ptr(gain), _ptr(accepted), _ptr(best_step),
+                                                _ptr(kempe_stats), self._stream(slot)))
 
     def lahc_kempe_aug(self, slot, room, rng, steps, history, p_swap=0.25, p_kempe=0.5, max_chain=0, room_rule=1,
                        scv=None, penalty=None, gain=None, accepted=None, best_step=None, kempe_stats=None):
@@ -561,20 +560,16 @@ class DeviceProblem:
         augmenting path). The optional tensors are lahc_kempe()'s, with
         kempe_stats int32 [P, 7]: its five counts, the chains a path rescued
         and the bystanders the accepted chains displaced."""
-        import torch
         P = self._pop(slot, room)
         self._rng(rng, P)
-        for name, t, n in (("scv", scv, P), ("penalty", penalty, P), ("gain", gain, P), ("accepted", accepted, P),
-                           ("best_step", best_step, P), ("kempe_stats", kempe_stats, 7 * P)):
-            if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n
-                                      and t.device == slot.device):
-                raise ValueError(f"{name} must be a contiguous int32 CUDA tensor of {'7 P' if n != P else 'P'} entries "
-                                 "on the population's device")
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)    # noqa: E731
+        for name, t in (("scv", scv), ("penalty", penalty), ("gain", gain), ("accepted", accepted),
+                        ("best_step", best_step)):
+            _opt_i32(name, t, P, "P", slot.device)
+        _opt_i32("kempe_stats", kempe_stats, 7 * P, "7 P" if P else "P", slot.device)
         _check(self.lib, self.lib.tt_lahc_kempe_aug(self.handle, slot.data_ptr(), room.data_ptr(), rng.data_ptr(), P,
                                                     int(steps), int(history), float(p_swap), float(p_kempe),
-                                                    int(max_chain), int(room_rule), ptr(scv), ptr(penalty), ptr(gain),
-                                                    ptr(accepted), ptr(best_step), ptr(kempe_stats),
+                                                    int(max_chain), int(room_rule), _ptr(scv), _ptr(penalty),
+                                                    _ptr(gain), _ptr(accepted), _ptr(best_step), _ptr(kempe_stats),
                                                     self._stream(slot)))
 
     # -- parallel walkers of the walk (include/ttga_lahc_multi.h) -----------------------
@@ -604,10 +599,7 @@ class DeviceProblem:
                                  ("accepted", accepted, P, "P"), ("best_step", best_step, P, "P"),
                                  ("kempe_stats", kempe_stats, 7 * P, "7 P"), ("winner", winner, P, "P"),
                                  ("walker_gain", walker_gain, max(K, 0) * P, "P * walkers")):
-            if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n
-                                      and t.device == slot.device):
-                raise ValueError(f"{name} must be a contiguous int32 CUDA tensor of {what} entries "
-                                 "on the population's device")
+            _opt_i32(name, t, n, what, slot.device)
         if work is None and 1 < K <= MAX_WALKERS and P * K < 2 ** 31:
             work = torch.empty(self.lahc_multi_work_bytes(P, K), dtype=torch.uint8, device=slot.device)
         if work is not None:
@@ -616,26 +608,18 @@ class DeviceProblem:
                     and (work.numel() >= need or need == 0)):
                 raise ValueError(f"work must be a contiguous uint8 CUDA tensor of at least {need} bytes "
                                  "on the population's device")
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)    # noqa: E731
         _check(self.lib, self.lib.tt_lahc_multi(self.handle, slot.data_ptr(), room.data_ptr(), rng.data_ptr(), P, K,
                                                 int(steps), int(history), float(p_swap), float(p_kempe),
-                                                int(max_chain), int(room_rule), ptr(scv), ptr(penalty), ptr(gain),
-                                                ptr(accepted), ptr(best_step), ptr(kempe_stats), ptr(winner),
-                                                ptr(walker_gain), ptr(work), self._stream(slot)))
+                                                int(max_chain), int(room_rule), _ptr(scv), _ptr(penalty), _ptr(gain),
+                                                _ptr(accepted), _ptr(best_step), _ptr(kempe_stats), _ptr(winner),
+                                                _ptr(walker_gain), _ptr(work), self._stream(slot)))
 
     # -- conflict-guided crossover (include/ttga_cx.h) -------------------------------
     def _cx_args(self, slot, order, P, cost, repaired):
-        import torch
-        if order is None:
-            order = self.greedy_order()
-        elif not (order.is_cuda and order.dtype == torch.int32 and order.is_contiguous() and order.numel() == self.E
-                  and order.device == slot.device):
-            raise ValueError("order must be a contiguous int32 CUDA tensor of E entries on the population's device")
+        _opt_i32("order", order, self.E, "E", slot.device)
         for name, t in (("cost", cost), ("repaired", repaired)):
-            if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == P
-                                      and t.device == slot.device):
-                raise ValueError(f"{name} must be a contiguous int32 CUDA tensor of P entries on the population's device")
-        return order
+            _opt_i32(name, t, P, "P", slot.device)
+        return self.greedy_order() if order is None else order
 
     def crossover_guided(self, slot1, slot2, rng, slot, room, order=None, repair=False, cost=None, repaired=None):
         """tt_crossover_guided: the counterpart of crossover; every event, in
@@ -648,10 +632,9 @@ class DeviceProblem:
             raise ValueError("the parents' tensors must have the children's shape [P, E]")
         self._rng(rng, P)
         order = self._cx_args(slot, order, P, cost, repaired)
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)    # noqa: E731
         _check(self.lib, self.lib.tt_crossover_guided(self.handle, slot1.data_ptr(), slot2.data_ptr(),
                                                       order.data_ptr(), rng.data_ptr(), slot.data_ptr(),
-                                                      room.data_ptr(), P, int(bool(repair)), ptr(cost), ptr(repaired),
+                                                      room.data_ptr(), P, int(bool(repair)), _ptr(cost), _ptr(repaired),
                                                       self._stream(slot)))
 
     def ga_breed_guided(self, pop_slot, pop_room, pop_penalty, rng, child_slot, child_room, child_flags,
@@ -663,11 +646,10 @@ class DeviceProblem:
         C = self._pop(child_slot, child_room)
         self._rng(rng, C)
         order = self._cx_args(child_slot, order, C, cost, repaired)
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)    # noqa: E731
         _check(self.lib, self.lib.tt_ga_breed_guided(
             self.handle, pop_slot.data_ptr(), pop_room.data_ptr(), pop_penalty.data_ptr(), N, order.data_ptr(),
             rng.data_ptr(), C, float(p_cross), float(p_mut), int(bool(skip_init_draws)), int(bool(repair)),
-            child_slot.data_ptr(), child_room.data_ptr(), child_flags.data_ptr(), ptr(cost), ptr(repaired),
+            child_slot.data_ptr(), child_room.data_ptr(), child_flags.data_ptr(), _ptr(cost), _ptr(repaired),
             self._stream(pop_slot)))
 
     @staticmethod
