@@ -5,35 +5,9 @@
 // TT_ERR_DEVICE and the null-handle checks run; with one, the argument checks
 // against a live handle (the device path is exercised by the GPU tests).
 #include <cstdio>
-#include <vector>
 
 #include "ttga_cx.h"
-
-namespace {
-
-struct Instance {
-    int E, R, F, S;
-    std::vector<int32_t> roomSize, studentEvents, roomFeatures, eventFeatures;
-};
-
-Instance make_instance() {
-    Instance in;
-    in.E = 70; in.R = 3; in.F = 2; in.S = 40;
-    in.roomSize.assign(in.R, 40);
-    in.studentEvents.resize(in.S * in.E);
-    in.roomFeatures.assign(in.R * in.F, 1);
-    in.eventFeatures.assign(in.E * in.F, 0);
-    for (int s = 0; s < in.S; ++s)
-        for (int e = 0; e < in.E; ++e) in.studentEvents[s * in.E + e] = (s * 7 + e * 3) % 11 == 0;
-    return in;
-}
-
-int fail(const char* what, int rc) {
-    std::printf("%s rc=%d: %s\n", what, rc, tt_last_error());
-    return rc ? rc : 10;
-}
-
-}  // namespace
+#include "boundary_common_cxx98.h"
 
 int main() {
     Instance in = make_instance();

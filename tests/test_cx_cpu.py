@@ -7,9 +7,7 @@ a C++98 consumer sees it, the argument handling before any device call, the
 crossover line."""
 import ctypes
 import pathlib
-import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,12 +16,13 @@ import ttga
 import cx_model as cm
 import greedy_model as gm
 from oracle_lib import oracle
+from stage_checks import (Sink, build_and_run_consumer, check_exports, rejected_by_native_driver,
+                          rejected_by_parse_control, stripped_before_pair_count)
 from ttga import native
 from ttga.ga import Island, crossover_line
 from ttga.islands import parse_control
 
 REPO = pathlib.Path(__file__).resolve().parent.parent
-PKG = REPO / "timetabling-ga-mpi-openmp_amd"
 HEADER = REPO / "include" / "ttga_cx.h"
 CONSUMER = REPO / "tests" / "boundary_cx_cxx98.cpp"
 
@@ -154,22 +153,8 @@ def test_guided_children_clash_less_than_uniform(sm_parents):
 
 
 # ---------------------------------------------------------------- the boundary
-def header_symbols():
-    return set(re.findall(r"\b(tt_[a-z_0-9]+)\s*\(", HEADER.read_text().split("#ifndef TTGA_CX_H")[1]))
-
-
 def test_header_symbols_are_exported_listed_and_called():
-    syms = header_symbols()
-    assert syms == {"tt_crossover_guided", "tt_ga_breed_guided"}
-    assert syms == set(native.CX_EXPORTS)
-    for other in (native.EXPORTS, native.REPORT_EXPORTS, native.UNIQUE_EXPORTS, native.GREEDY_EXPORTS,
-                  native.KEMPE_EXPORTS, native.SLOTSWAP_EXPORTS, native.LAHC_EXPORTS):
-        assert not syms & set(other)
-    lib = native.load()
-    for s in syms:
-        assert hasattr(lib, s), s
-    called = set(re.findall(r"\b(tt_[a-z_0-9]+)\s*\(", CONSUMER.read_text()))
-    assert syms <= called, sorted(syms - called)
+    check_exports(HEADER, "TTGA_CX_H", "CX_EXPORTS", CONSUMER, {"tt_crossover_guided", "tt_ga_breed_guided"})
     text = HEADER.read_text()
     assert '#include "ttga.h"' in text and "no counterpart in the reference" in text and "ga.cpp:562-566" in text
     top = (REPO / "include" / "ttga.h").read_text()
@@ -178,17 +163,7 @@ def test_header_symbols_are_exported_listed_and_called():
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_cxx98_cx_consumer_builds_and_links(tmp_path):
-    exe = tmp_path / "consumer"
-    r = subprocess.run(["g++", "-Wall", "-ansi", "-O3", "-pedantic", "-Werror", "-I", str(REPO / "include"),
-                        str(CONSUMER), "-L", str(PKG), "-lttga", f"-Wl,-rpath,{PKG}", "-o", str(exe)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0 and r.stderr == "", r.stderr
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert run.returncode in (0, 2), run.stdout + run.stderr
-    if run.returncode == 2:
-        assert "TT_ERR_DEVICE" in run.stdout and "null-handle checks: 0 wrong" in run.stdout
-    else:
-        assert "null-buffer checks: 0 wrong" in run.stdout
+    build_and_run_consumer(CONSUMER, tmp_path)
 
 
 def test_argument_errors_without_a_device():
@@ -242,14 +217,6 @@ def test_argument_errors_without_a_device():
 
 
 # ---------------------------------------------------------------- the flags, Island, the line
-class Sink:
-    def __init__(self):
-        self.text = ""
-
-    def write(self, s):
-        self.text += s
-
-
 BAD_FLAGS = ((["-i", "x.tim", "--crossover", "best"], "--crossover must be uniform or guided"),
              (["-i", "x.tim", "--crossover"], "--crossover must be uniform or guided"),
              (["-i", "x.tim", "--crossover", "Guided"], "--crossover must be uniform or guided"),
@@ -268,22 +235,13 @@ def test_crossover_flags_in_the_control_parse():
     assert ctl["crossover"] == "uniform"
     assert "crossover" not in parse_control(["-i", "x.tim", "-s", "42"], out=Sink(), err=Sink())
     for bad, msg in BAD_FLAGS:
-        err = Sink()
-        with pytest.raises(SystemExit) as ex:
-            parse_control(bad, out=Sink(), err=err)
-        assert ex.value.code == 1 and msg in err.text
+        rejected_by_parse_control(bad, msg, exact=True)
 
 
 def test_crossover_flags_in_the_native_driver():
-    exe = PKG / "ttga-ga"
-    assert exe.exists(), "ttga-ga not built (make -C timetabling-ga-mpi-openmp_amd)"
     for bad, msg in BAD_FLAGS:
-        r = subprocess.run([str(exe), *bad], capture_output=True, text=True, timeout=60)
-        assert r.returncode == 1 and msg in r.stderr, (bad, r.stderr)
-    # the flags and the value are stripped before the pair count
-    r = subprocess.run([str(exe), "--crossover", "guided", "--crossover-repair", "-s"], capture_output=True, text=True,
-                       timeout=60)
-    assert r.returncode == 1 and "Parse error: Number of command line parameters incorrect" in r.stderr
+        rejected_by_native_driver(bad, msg, exact=True)
+    stripped_before_pair_count(["--crossover", "guided", "--crossover-repair"])
 
 
 def test_island_checks_its_crossover_arguments_before_any_device_call():

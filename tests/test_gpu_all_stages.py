@@ -6,15 +6,14 @@ print the same lines (each island's logEntry lines in the same order; between
 islands their order is the native driver's threads' and not fixed), the stage
 lines byte for byte and in the documented order, and the stage lines count the
 rows they should."""
-import os
 import pathlib
-import subprocess
 import sys
 
 import pytest
 
 import ttga
 from helpers import json_lines
+from stage_checks import run_driver
 
 pytestmark = pytest.mark.gpu
 
@@ -24,13 +23,6 @@ STAGE_KINDS = ("crossover", "kempe", "unique", "slotSwap", "lahc")
 ARGS = ["-s", "29", "-p", "1", "--pop", "16", "--children", "8", "--generations", "60", "--islands", "2",
         "--init", "greedy", "--unique", "--kempe", "0.5", "--kempe-max-chain", "4", "--slot-swap", "1",
         "--lahc", "200", "--lahc-history", "100", "--crossover", "guided", "--crossover-repair"]
-
-
-def _run(cmd, cwd):
-    env = dict(os.environ, PYTHONPATH=str(PKG))
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=str(cwd))
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r
 
 
 def _per_island(lines):
@@ -53,8 +45,8 @@ def test_all_stages_in_both_drivers(tmp_path, stagger):
     exe = PKG / "ttga-ga"
     assert exe.exists(), "ttga-ga not built (make -C timetabling-ga-mpi-openmp_amd)"
     args = ["-i", str(tim), *ARGS, *(["--stagger"] if stagger else [])]
-    py = _run([sys.executable, "-m", "ttga.islands", *args], tmp_path)
-    cc = _run([str(exe), *args], tmp_path)
+    py = run_driver([sys.executable, "-m", "ttga.islands", *args], tmp_path)
+    cc = run_driver([str(exe), *args], tmp_path)
     a, b = json_lines(py.stdout), json_lines(cc.stdout)
     assert _per_island(a) == _per_island(b) and a
 

@@ -6,10 +6,7 @@ GPU's own rows; a caller's and an invalid order; parents' genes >= 45;
 tt_ga_breed_guided against the model's breed and against tt_ga_breed; the limit;
 the point of it (fewer hard violations than the uniform children); Island with
 crossover="guided"; and the two drivers with --crossover guided."""
-import os
 import pathlib
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -19,6 +16,7 @@ import cx_model as cm
 import greedy_model as gm
 from helpers import dev, host, json_lines
 from oracle_lib import oracle
+from stage_checks import GA, both_drivers, run_driver
 
 pytestmark = pytest.mark.gpu
 
@@ -28,7 +26,6 @@ from ttga.ga import Island, stream_seeds  # noqa: E402
 from ttga.rng import random_slots  # noqa: E402
 
 REPO = pathlib.Path(__file__).resolve().parent.parent
-PKG = REPO / "timetabling-ga-mpi-openmp_amd"
 BAD_ORDER = 512                                             # tt_device_status bit 9
 
 # seeds: 1, the largest in-range state, 0 (the stream stays 0), one above 2^31
@@ -503,36 +500,16 @@ def test_island_uniform_issues_no_guided_call(problems, variant, monkeypatch):
 
 
 # ---------------------------------------------------------------- the drivers
-def _run(cmd, cwd):
-    env = dict(os.environ, PYTHONPATH=str(PKG))
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=str(cwd))
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r
-
-
 def test_crossover_guided_in_both_drivers(tmp_path):
     tim = REPO / "tests" / "golden" / "sm.tim"
     inst = ttga.read_tim(tim)
-    exe = PKG / "ttga-ga"
-    assert exe.exists(), "ttga-ga not built (make -C timetabling-ga-mpi-openmp_amd)"
     base = ["-i", str(tim), "-s", "29", "-p", "1", "--pop", "16", "--children", "8", "--generations", "10",
             "--kempe", "0.5"]
-    flags = ["--crossover", "guided", "--crossover-repair"]
-    py = _run([sys.executable, "-m", "ttga.islands", *base, *flags], tmp_path)
-    cc = _run([str(exe), *flags, *base], tmp_path)
-    cc_plain = _run([str(exe), *base, "--crossover", "uniform"], tmp_path)
-    a, b = json_lines(py.stdout), json_lines(cc.stdout)
-    assert a == b and a
-    assert [ln for ln in py.stdout.splitlines() if ln.startswith('{"crossover"')] == \
-           [ln for ln in cc.stdout.splitlines() if ln.startswith('{"crossover"')]        # byte for byte
-    lines = [x["crossover"] for x in a if "crossover" in x]
+    py, cc, a, lines = both_drivers(tmp_path, base, ["--crossover", "guided", "--crossover-repair"], "crossover", inst)
+    cc_plain = run_driver([str(GA), *base, "--crossover", "uniform"], tmp_path)
     assert len(lines) == 1 and set(lines[0]) == {"children", "clean", "crossed", "meanCost", "repaired"}
     k = lines[0]
     assert k["children"] == 80 and 0 < k["crossed"] <= 80 and 0 <= k["clean"] <= k["crossed"] and k["repaired"] > 0
     kinds = [next(iter(x)) for x in a]
     assert kinds.index("crossover") == kinds.index("solution") + 1 == kinds.index("kempe") - 1
     assert not any("crossover" in x for x in json_lines(cc_plain.stdout))          # uniform: no call, no line
-    from ttga.validate import check_text
-    for r_ in (py, cc):
-        reps = check_text(inst, r_.stdout)
-        assert reps and all(x["ok"] for x in reps), reps

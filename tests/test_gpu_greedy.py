@@ -4,7 +4,6 @@ model's slots through the oracle's assign_rooms) and final Random states bit
 for bit; the replay check (no RNG) on the GPU's own rows; the limit and an
 invalid order; Island(init="greedy"); its effect on the local search; and the
 two drivers with --init greedy."""
-import os
 import pathlib
 import subprocess
 import sys
@@ -16,6 +15,7 @@ import ttga
 import greedy_model as gm
 from helpers import dev, host, json_lines
 from oracle_lib import oracle
+from stage_checks import GA, both_drivers, run_driver
 
 pytestmark = pytest.mark.gpu
 
@@ -299,27 +299,15 @@ def test_greedy_start_makes_the_search_feasible(orc):
 
 
 # ---------------------------------------------------------------- the drivers
-def _run(cmd, cwd):
-    env = dict(os.environ, PYTHONPATH=str(PKG))
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=str(cwd))
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r
-
-
 def test_init_greedy_in_both_drivers(tmp_path, problems):
     inst, dp, _ = problems("sm")
     tim = tmp_path / "sm.tim"
     ttga.write_tim(inst, tim)
-    exe = PKG / "ttga-ga"
-    assert exe.exists(), "ttga-ga not built (make -C timetabling-ga-mpi-openmp_amd)"
     base = ["-i", str(tim), "-s", "29", "-p", "1", "--pop", "16", "--children", "8", "--generations", "10"]
-    py = _run([sys.executable, "-m", "ttga.islands", *base, "--init", "greedy"], tmp_path)
-    cc = _run([str(exe), "--init", "greedy", *base], tmp_path)
-    py_plain = _run([sys.executable, "-m", "ttga.islands", *base], tmp_path)
-    cc_plain = _run([str(exe), *base], tmp_path)
-    cc_random = _run([str(exe), *base, "--init", "random"], tmp_path)
-    a, b = json_lines(py.stdout), json_lines(cc.stdout)
-    assert a == b and a
+    py, cc, a, _ = both_drivers(tmp_path, base, ["--init", "greedy"], None, inst)       # the stage prints no line
+    py_plain = run_driver([sys.executable, "-m", "ttga.islands", *base], tmp_path)
+    cc_plain = run_driver([str(GA), *base], tmp_path)
+    cc_random = run_driver([str(GA), *base, "--init", "random"], tmp_path)
     plain = json_lines(py_plain.stdout)
     assert plain == json_lines(cc_plain.stdout) == json_lines(cc_random.stdout)
     assert a != plain                                        # another initial population
@@ -332,10 +320,7 @@ def test_init_greedy_in_both_drivers(tmp_path, problems):
     k = int(np.argmin(pen.astype(np.uint32)))
     first = [x["logEntry"] for x in a if "logEntry" in x][0]
     assert first["best"] == (int(sc[k]) if f[k] else int(h[k]) * 1000000 + int(sc[k]))
-    from ttga.validate import check_text
     for r_ in (py, cc):
-        reps = check_text(inst, r_.stdout)
-        assert reps and all(x["ok"] for x in reps), reps
         out = subprocess.run([str(PKG / "ttga-check"), str(tim), "-"], input=r_.stdout, capture_output=True, text=True,
                              timeout=60)
         assert out.returncode == 0, out.stdout

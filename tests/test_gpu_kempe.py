@@ -4,10 +4,8 @@ rooms of the two touched slots against the oracle's assign_rooms of the model's
 new slot row and every other room unchanged; the gate, the cap, crowded slots,
 invalid genes, chain_len = NULL, the limit, Island(kempe=...) and the two
 drivers with --kempe."""
-import os
 import pathlib
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -16,6 +14,7 @@ import ttga
 import kempe_model as km
 from helpers import dev, host, json_lines
 from oracle_lib import oracle
+from stage_checks import GA, both_drivers, run_driver
 
 pytestmark = pytest.mark.gpu
 
@@ -329,27 +328,13 @@ def test_island_against_explicit_calls(problems):
 
 
 # ---------------------------------------------------------------- the drivers
-def _run(cmd, cwd):
-    env = dict(os.environ, PYTHONPATH=str(PKG))
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=str(cwd))
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r
-
-
 def test_kempe_in_both_drivers(tmp_path, problems):
     inst = problems("sm")[0]
     tim = tmp_path / "sm.tim"
     ttga.write_tim(inst, tim)
-    exe = PKG / "ttga-ga"
-    assert exe.exists(), "ttga-ga not built (make -C timetabling-ga-mpi-openmp_amd)"
     base = ["-i", str(tim), "-s", "29", "-p", "1", "--pop", "16", "--children", "8", "--generations", "10"]
-    flags = ["--kempe", "0.5", "--kempe-max-chain", "8"]
-    py = _run([sys.executable, "-m", "ttga.islands", *base, *flags], tmp_path)
-    cc = _run([str(exe), *flags, *base], tmp_path)
-    cc_zero = _run([str(exe), *base, "--kempe", "0"], tmp_path)
-    a, b = json_lines(py.stdout), json_lines(cc.stdout)
-    assert a == b and a
-    kempe = [x["kempe"] for x in a if "kempe" in x]
+    py, cc, a, kempe = both_drivers(tmp_path, base, ["--kempe", "0.5", "--kempe-max-chain", "8"], "kempe", inst)
+    cc_zero = run_driver([str(GA), *base, "--kempe", "0"], tmp_path)
     assert len(kempe) == 1 and set(kempe[0]) == {"children", "moved", "rejected", "meanChain"}
     k = kempe[0]
     assert k["children"] == 80 and 0 < k["moved"] and 0 <= k["rejected"] and k["moved"] + k["rejected"] < 80
@@ -357,10 +342,7 @@ def test_kempe_in_both_drivers(tmp_path, problems):
     kinds = [next(iter(x)) for x in a]
     assert kinds[kinds.index("kempe") - 1] == "solution"      # after its island's solution line
     assert not any("kempe" in x for x in json_lines(cc_zero.stdout))     # probability 0: no call, no line
-    from ttga.validate import check_text
     for r_ in (py, cc):
-        reps = check_text(inst, r_.stdout)
-        assert reps and all(x["ok"] for x in reps), reps
         out = subprocess.run([str(PKG / "ttga-check"), str(tim), "-"], input=r_.stdout, capture_output=True, text=True,
                              timeout=60)
         assert out.returncode == 0, out.stdout

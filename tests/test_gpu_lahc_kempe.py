@@ -5,9 +5,7 @@ launch, and around every call tt_eval: hcv 0, scv lower by exactly the gain,
 the scv / penalty updated in place equal to a fresh evaluation. Then the call
 without chains against tt_lahc, invalid genes and arguments, the LDS limit,
 Island(lahc_kempe=...) and the two drivers with --lahc-kempe."""
-import os
 import pathlib
-import subprocess
 import sys
 
 import numpy as np
@@ -16,17 +14,16 @@ import pytest
 import ttga
 import lahc_kempe_model as km
 import lahc_model as lm
-from helpers import dev, host, json_lines
+import walk_checks as wc
+from helpers import host, json_lines
+from stage_checks import GA, VARIANTS, both_drivers, run_driver, run_island, stage_lines
+from walk_checks import BAD_GENE, NAMES
 
 pytestmark = pytest.mark.gpu
 
-import torch  # noqa: E402
 from ttga import native  # noqa: E402
-from test_gpu_lahc import VARIANTS, run_island  # noqa: E402
 
 REPO = pathlib.Path(__file__).resolve().parent.parent
-PKG = REPO / "timetabling-ga-mpi-openmp_amd"
-BAD_GENE = 256                                   # tt_device_status bit 8
 
 # id: (shape, P, steps, history, p_swap, p_kempe, max_chain)
 CASES = {
@@ -44,7 +41,6 @@ CASES = {
     "steps0": ("sm", 33, 0, 50, 0.25, 0.5, 0), "steps1": ("sm", 33, 1, 50, 0.25, 0.5, 0),
     "tight": ("tight", 33, 1000, 50, 0.25, 0.5, 0),
 }
-NAMES = ("slot", "room", "rng", "gain", "accepted", "best_step", "kempe_stats")
 
 
 @pytest.fixture(scope="module")
@@ -59,47 +55,27 @@ def problems():
     return get
 
 
-def run(dp, slot, room, seeds, steps, L, p_swap, p_kempe, cap, with_eval=True, call=None):
-    """One call on numpy rows; returns the outputs and the evaluations around it."""
-    P = slot.shape[0]
-    s, r, g = dev(slot), dev(room), dev(seeds)
-    before = [host(t) for t in dp.eval(s, r)] if with_eval else None
-    scv = dev(before[1]) if with_eval else None
-    pen = dev(before[3]) if with_eval else None
-    out = [torch.full((P,), 12345, dtype=torch.int32, device="cuda") for _ in range(3)]
-    stats = torch.full((P, 5), 12345, dtype=torch.int32, device="cuda")
-    if call is None:
-        dp.lahc_kempe(s, r, g, steps, L, p_swap, p_kempe, cap, scv=scv, penalty=pen, gain=out[0], accepted=out[1],
-                      best_step=out[2], kempe_stats=stats)
-    else:
-        call(s, r, g, scv, pen, out)
-    got = (host(s), host(r), host(g), host(out[0]), host(out[1]), host(out[2]), host(stats))
-    after = [host(t) for t in dp.eval(s, r)] if with_eval else None
-    return got, before, after, (host(scv), host(pen)) if with_eval else None
+def call(dp, a):
+    return lambda s, r, g, **out: dp.lahc_kempe(s, r, g, a["steps"], a["history"], a["p_swap"], a["p_kempe"],
+                                                a["max_chain"], **out)
+
+
+def rows(model, slot, room, seeds, a, infos=None):
+    return model.lahc_kempe_rows(slot, room, seeds, a["steps"], a["history"], a["p_swap"], a["p_kempe"], a["max_chain"],
+                                 infos)
+
+
+def walk_args(steps, L, p_swap, p_kempe, cap=0):
+    return dict(steps=steps, history=L, p_swap=p_swap, p_kempe=p_kempe, max_chain=cap)
 
 
 def check(problem, slot, room, seeds, steps, L, p_swap, p_kempe, cap, infos=None):
     inst, dp, model = problem
-    P = slot.shape[0]
-    want = model.lahc_kempe_rows(slot, room, seeds, steps, L, p_swap, p_kempe, cap, infos)
-    got, before, after, inplace = run(dp, slot, room, seeds, steps, L, p_swap, p_kempe, cap)
-    for name, g, w in zip(NAMES, got, want):
-        diff = np.flatnonzero((g.reshape(P, -1) != w.reshape(P, -1)).any(axis=1))
-        assert diff.size == 0, f"{name} differs in rows {diff[:8]}: gpu {g[diff[:2]]} model {w[diff[:2]]}"
-    hcv0, scv0, feas0, pen0 = before
-    hcv1, scv1, feas1, pen1 = after
-    assert np.array_equal(hcv1, hcv0) and np.array_equal(feas1, feas0)
-    assert np.array_equal(scv1, scv0 - got[3]) and (got[3] >= 0).all()
-    assert np.array_equal(inplace[0], scv1) and np.array_equal(inplace[1], pen1)      # in place = a fresh tt_eval
-    closed = hcv0 != 0                                                               # rows the gate keeps out
-    assert np.array_equal(got[0][closed], slot[closed]) and np.array_equal(got[1][closed], room[closed])
-    assert np.array_equal(got[2][closed], seeds[closed])
-    assert not got[3][closed].any() and not got[4][closed].any() and not got[5][closed].any()
-    assert not got[6][closed].any()
-    assert (got[5] <= steps).all() and (got[4] <= steps).all()
-    st = got[6].astype(np.int64)
-    assert (st[:, 3] <= st[:, 0] - st[:, 1] - st[:, 2]).all() and (st[:, 3] <= got[4]).all()
-    return got, want, hcv0
+    a = walk_args(steps, L, p_swap, p_kempe, cap)
+    want = rows(model, slot, room, seeds, a, infos)
+    got, before, after, inplace = wc.run(dp, call(dp, a), slot, room, seeds, 5)
+    wc.check_rows(got, want, before, after, inplace, slot, room, seeds, steps)
+    return got, want, before[0]
 
 
 @pytest.mark.parametrize("cid", list(CASES))
@@ -126,13 +102,7 @@ def test_rows_vs_model(problems, cid):
     if steps == 0:
         assert not got[4].any() and not got[6].any() and np.array_equal(got[0], slot) and np.array_equal(got[2], seeds)
         return
-    # the streams of the searched rows advanced by exactly 3 * steps draws
-    from ttga.rng import step
-    i = int(np.flatnonzero(hcv0 == 0)[0])
-    s = int(seeds[i])
-    for _ in range(3 * steps):
-        s = step(s)
-    assert got[2][i] == s
+    wc.check_stream_advance(got, seeds, hcv0 != 0, 3 * steps)      # exactly 3 * steps draws a searched row
     assert k_acc == kinds["kempe"] == len(chains) and events == sum(chains)
     if steps > 1:
         assert got[4].sum() > 0 and tried > 0
@@ -171,10 +141,8 @@ def test_without_chains_the_call_is_tt_lahc(problems, p_swap):
     inst, dp, model = problems("sm")
     slot, room, seeds = lm.population(inst, 33, model)
 
-    def plain(s, r, g, scv, pen, out):
-        dp.lahc(s, r, g, 1000, 50, p_swap, scv=scv, penalty=pen, gain=out[0], accepted=out[1], best_step=out[2])
-    a = run(dp, slot, room, seeds, 1000, 50, p_swap, 0.0, 3)
-    b = run(dp, slot, room, seeds, 1000, 50, p_swap, 0.0, 0, call=plain)
+    a = wc.run(dp, call(dp, walk_args(1000, 50, p_swap, 0.0, 3)), slot, room, seeds, 5)
+    b = wc.run(dp, lambda s, r, g, **out: dp.lahc(s, r, g, 1000, 50, p_swap, **out), slot, room, seeds)
     for name, x, y in zip(NAMES[:6], a[0], b[0]):
         assert np.array_equal(x, y), name
     assert not a[0][6].any() and a[0][4].sum() > 0
@@ -182,71 +150,25 @@ def test_without_chains_the_call_is_tt_lahc(problems, p_swap):
 
 
 # ---------------------------------------------------------------- invalid genes, errors, the limit
+OK = walk_args(10, 5, 0.25, 0.5)
+BAD = (dict(steps=-1), dict(history=0), dict(history=-3), dict(p_swap=1.5, p_kempe=0.0), dict(p_swap=-0.1),
+       dict(p_swap=float("nan")), dict(p_kempe=1.5, p_swap=0.0), dict(p_kempe=-0.1), dict(p_kempe=float("nan")),
+       dict(max_chain=-1), dict(p_swap=0.75, p_kempe=0.5), dict(p_swap=0.25, p_kempe=1.0))
+
+
 def test_invalid_genes():
-    """Rows with slot gene 45 / room gene R between valid ones: untouched, rng
-    included, outputs 0, status bit 8; their neighbours walk as the model has
-    them. Own handle: the status word is sticky."""
-    inst = lm.SHAPES["sm"]()
-    dp, model = native.DeviceProblem(inst), km.Model(inst)
-    slot, room, seeds = lm.population(inst, 6, model)
-    slot[1, 7] = 45
-    room[4, 3] = inst.R
-    assert dp.status() == 0
-    want = model.lahc_kempe_rows(slot, room, seeds, 500, 50, 0.25, 0.5)
-    got, _, _, _ = run(dp, slot, room, seeds, 500, 50, 0.25, 0.5, 0, with_eval=False)
-    for name, g, w in zip(NAMES, got, want):
-        assert np.array_equal(g, w), name
-    for i in (1, 4):
-        assert np.array_equal(got[0][i], slot[i]) and np.array_equal(got[1][i], room[i]) and got[2][i] == seeds[i]
-        assert got[3][i] == got[4][i] == got[5][i] == 0 and not got[6][i].any()
-    assert got[4][0] > 0 and got[4][3] > 0 and got[4][5] > 0
-    assert dp.status() & BAD_GENE == BAD_GENE
-    dp.close()
+    wc.invalid_genes(km.Model, call, rows, walk_args(500, 50, 0.25, 0.5), 5)
 
 
 def test_invalid_arguments_launch_nothing(problems):
-    inst, dp, model = problems("sm")
-    slot, room, seeds = lm.population(inst, 4, model)
-    s, r, g = dev(slot), dev(room), dev(seeds)
-    out = [torch.full((4,), 12345, dtype=torch.int32, device="cuda") for _ in range(5)]
-    stats = torch.full((4, 5), 12345, dtype=torch.int32, device="cuda")
-    ok = dict(steps=10, history=5, p_swap=0.25, p_kempe=0.5, max_chain=0)
-    for kw in (dict(steps=-1), dict(history=0), dict(history=-3), dict(p_swap=1.5, p_kempe=0.0), dict(p_swap=-0.1),
-               dict(p_swap=float("nan")), dict(p_kempe=1.5, p_swap=0.0), dict(p_kempe=-0.1),
-               dict(p_kempe=float("nan")), dict(max_chain=-1), dict(p_swap=0.75, p_kempe=0.5),
-               dict(p_swap=0.25, p_kempe=1.0)):
-        a = {**ok, **kw}
-        with pytest.raises(native.TTError) as ei:
-            dp.lahc_kempe(s, r, g, a["steps"], a["history"], a["p_swap"], a["p_kempe"], a["max_chain"], scv=out[0],
-                          penalty=out[1], gain=out[2], accepted=out[3], best_step=out[4], kempe_stats=stats)
-        assert ei.value.code == native.TT_ERR_INVALID, kw
-    assert np.array_equal(host(s), slot) and np.array_equal(host(r), room) and np.array_equal(host(g), seeds)
-    assert all((host(t) == 12345).all() for t in out + [stats])
-    # every output NULL
-    dp.lahc_kempe(s, r, g, 200, 20, 0.25, 0.5)
-    want = model.lahc_kempe_rows(slot, room, seeds, 200, 20, 0.25, 0.5)
-    assert np.array_equal(host(s), want[0]) and np.array_equal(host(r), want[1]) and np.array_equal(host(g), want[2])
+    wc.invalid_arguments_launch_nothing(problems("sm"), call, rows, OK, BAD,
+                                        lambda dp, s, r, g: dp.lahc_kempe(s, r, g, 200, 20, 0.25, 0.5), 5)
 
 
 def test_limit(problems):
-    """A history too long for the LDS: TT_ERR_LIMIT, every buffer untouched.
-    The header's formula for sm (E 100, S 80) without the history:
+    """The header's formula for sm (E 100, S 80) without the history:
     8 * (47 * 2 + 45 + 80) + 4 * 100 + 1,168 = 3,320 bytes."""
-    inst, dp, model = problems("sm")
-    slot, room, seeds = lm.population(inst, 4, model)
-    s, r, g = dev(slot), dev(room), dev(seeds)
-    out = [torch.full((4,), 12345, dtype=torch.int32, device="cuda") for _ in range(5)]
-    stats = torch.full((4, 5), 12345, dtype=torch.int32, device="cuda")
-    fits = (65536 - 3320) // 4
-    with pytest.raises(native.TTError, match="too large") as ei:
-        dp.lahc_kempe(s, r, g, 10, fits + 1, 0.25, 0.5, 0, scv=out[0], penalty=out[1], gain=out[2], accepted=out[3],
-                      best_step=out[4], kempe_stats=stats)
-    assert ei.value.code == native.TT_ERR_LIMIT
-    assert np.array_equal(host(s), slot) and np.array_equal(host(r), room) and np.array_equal(host(g), seeds)
-    assert all((host(t) == 12345).all() for t in out + [stats])
-    dp.lahc_kempe(s, r, g, 10, fits, 0.25, 0.5, 0, gain=out[2], kempe_stats=stats)   # the largest history that fits
-    want = model.lahc_kempe_rows(slot, room, seeds, 10, fits, 0.25, 0.5)
-    assert np.array_equal(host(out[2]), want[3]) and np.array_equal(host(stats), want[6])
+    wc.lds_limit(problems("sm"), call, rows, OK, 3320, 5)
 
 
 # ---------------------------------------------------------------- Island
@@ -292,33 +214,15 @@ def test_island_lahc_kempe_0_never_calls_the_new_binding(problems, monkeypatch):
 
 
 # ---------------------------------------------------------------- the drivers
-def _run(cmd, cwd):
-    env = dict(os.environ, PYTHONPATH=str(PKG))
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=str(cwd))
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r
-
-
-def _lines(text, key):
-    return [ln for ln in text.splitlines() if ln.startswith('{"%s"' % key)]
-
-
 def test_lahc_kempe_in_both_drivers(tmp_path):
     tim = REPO / "tests" / "golden" / "sm.tim"
     inst = ttga.read_tim(tim)
-    exe = PKG / "ttga-ga"
-    assert exe.exists(), "ttga-ga not built (make -C timetabling-ga-mpi-openmp_amd)"
     base = ["-i", str(tim), "-s", "29", "-p", "1", "--pop", "16", "--children", "8", "--generations", "10",
             "--init", "greedy"]
     flags = ["--lahc", "500", "--lahc-history", "100", "--lahc-swap", "0.25", "--lahc-kempe", "0.5",
              "--lahc-kempe-max-chain", "8"]
-    py = _run([sys.executable, "-m", "ttga.islands", *base, *flags], tmp_path)
-    cc = _run([str(exe), *flags, *base], tmp_path)
-    a, b = json_lines(py.stdout), json_lines(cc.stdout)
-    assert a == b and a
-    assert _lines(py.stdout, "lahcKempe") == _lines(cc.stdout, "lahcKempe")               # byte for byte
-    assert _lines(py.stdout, "lahc") == _lines(cc.stdout, "lahc")
-    lines = [x["lahcKempe"] for x in a if "lahcKempe" in x]
+    py, cc, a, lines = both_drivers(tmp_path, base, flags, "lahcKempe", inst)
+    assert stage_lines(py.stdout, "lahc") == stage_lines(cc.stdout, "lahc")              # byte for byte
     assert len(lines) == 1 and set(lines[0]) == {"tried", "capped", "noRoom", "accepted", "meanChain"}
     k = lines[0]
     walk = [x["lahc"] for x in a if "lahc" in x]
@@ -327,10 +231,6 @@ def test_lahc_kempe_in_both_drivers(tmp_path):
     assert k["accepted"] <= walk[0]["accepted"] and walk[0]["rows"] == 16 + 80
     kinds = [next(iter(x)) for x in a]
     assert kinds.index("lahcKempe") == kinds.index("lahc") + 1 > kinds.index("solution")
-    from ttga.validate import check_text
-    for r_ in (py, cc):
-        reps = check_text(inst, r_.stdout)
-        assert reps and all(x["ok"] for x in reps), reps
 
 
 def test_all_stages_with_lahc_kempe_in_both_drivers(tmp_path):
@@ -339,10 +239,9 @@ def test_all_stages_with_lahc_kempe_in_both_drivers(tmp_path):
     kinds_all = STAGE_KINDS + ("lahcKempe",)
     tim = REPO / "tests" / "golden" / "sm.tim"
     inst = ttga.read_tim(tim)
-    exe = PKG / "ttga-ga"
     args = ["-i", str(tim), *ARGS, "--lahc-swap", "0.25", "--lahc-kempe", "0.5", "--lahc-kempe-max-chain", "6"]
-    py = _run([sys.executable, "-m", "ttga.islands", *args], tmp_path)
-    cc = _run([str(exe), *args], tmp_path)
+    py = run_driver([sys.executable, "-m", "ttga.islands", *args], tmp_path)
+    cc = run_driver([str(GA), *args], tmp_path)
     a, b = json_lines(py.stdout), json_lines(cc.stdout)
     assert _per_island(a) == _per_island(b) and a
 

@@ -8,9 +8,7 @@ of tt_lahc_kempe_aug on copies of the rows, the winner picked by torch. Then one
 walker against tt_lahc_kempe_aug, tt_lahc_kempe and tt_lahc, the edges, invalid
 genes and arguments, the limits, two streams, Island(lahc_walkers=K) and the two
 drivers with --lahc-walkers."""
-import os
 import pathlib
-import subprocess
 import sys
 
 import numpy as np
@@ -19,19 +17,17 @@ import pytest
 import ttga
 import lahc_model as lm
 import lahc_multi_model as mm
+import walk_checks as wc
 from helpers import dev, host, json_lines
+from stage_checks import GA, both_drivers, run_driver, run_island, stage_lines
+from walk_checks import BAD_GENE, FILL, NAMES, same
 
 pytestmark = pytest.mark.gpu
 
 import torch  # noqa: E402
 from ttga import native  # noqa: E402
-from ttga.ga import Island  # noqa: E402
 
 REPO = pathlib.Path(__file__).resolve().parent.parent
-PKG = REPO / "timetabling-ga-mpi-openmp_amd"
-BAD_GENE = 256                                   # tt_device_status bit 8
-NAMES = ("slot", "room", "rng", "gain", "accepted", "best_step", "kempe_stats", "winner", "walker_gain")
-FILL = 12345
 SEEN = {"later": 0, "idle": 0, "cases": 0}      # over test_rows_vs_model's cases
 
 
@@ -49,47 +45,33 @@ def problems():
 
 def outputs(P, K):
     """gain, accepted, best_step [P], kempe_stats [P, 7], winner [P], walker_gain [P, K], sentinel-filled."""
-    full = lambda *shape: torch.full(shape, FILL, dtype=torch.int32, device="cuda")      # noqa: E731
-    return [full(P), full(P), full(P), full(P, 7), full(P), full(P, K)]
+    return [wc.filled(P), wc.filled(P), wc.filled(P), wc.filled(P, 7), wc.filled(P), wc.filled(P, K)]
+
+
+def call(dp, a):
+    """tt_lahc_multi for walk_checks.run; work "own": a tensor of the documented size, None: the binding's."""
+    def launch(s, r, g, **out):
+        work = a.get("work", "own")
+        if isinstance(work, str):
+            work = torch.empty(dp.lahc_multi_work_bytes(s.shape[0], a["K"]), dtype=torch.uint8, device="cuda")
+        dp.lahc_multi(s, r, g, a["K"], a["steps"], a["history"], a["p_swap"], a["p_kempe"], a.get("max_chain", 0),
+                      a.get("room_rule", 1), work=work, **out)
+    return launch
+
+
+def rows(model, slot, room, seeds, a):
+    return model.lahc_multi_rows(slot, room, seeds, a["K"], a["steps"], a["history"], a["p_swap"], a["p_kempe"])
 
 
 def run(dp, slot, room, seeds, K, steps, L, p_swap, p_kempe, cap=0, rule=1, with_eval=True, work="own"):
     """One call on numpy rows; returns the outputs and the evaluations around it."""
-    P = slot.shape[0]
-    s, r, g = dev(slot), dev(room), dev(seeds)
-    before = [host(t) for t in dp.eval(s, r)] if with_eval else None
-    scv = dev(before[1]) if with_eval else None
-    pen = dev(before[3]) if with_eval else None
-    out = outputs(P, K)
-    if work == "own":
-        work = torch.empty(dp.lahc_multi_work_bytes(P, K), dtype=torch.uint8, device="cuda")
-    dp.lahc_multi(s, r, g, K, steps, L, p_swap, p_kempe, cap, rule, scv=scv, penalty=pen, gain=out[0], accepted=out[1],
-                  best_step=out[2], kempe_stats=out[3], winner=out[4], walker_gain=out[5], work=work)
-    got = (host(s), host(r), host(g), *(host(t) for t in out))
-    after = [host(t) for t in dp.eval(s, r)] if with_eval else None
-    return got, before, after, (host(scv), host(pen)) if with_eval else None
+    a = dict(K=K, steps=steps, history=L, p_swap=p_swap, p_kempe=p_kempe, max_chain=cap, room_rule=rule, work=work)
+    return wc.run(dp, call(dp, a), slot, room, seeds, 7, with_eval, winner=(), walker_gain=(K,))
 
 
-def same(got, want, names=NAMES):
-    P = got[0].shape[0]
-    for name, g, w in zip(names, got, want):
-        assert g.shape == w.shape, name
-        diff = np.flatnonzero((g.reshape(P, -1) != w.reshape(P, -1)).any(axis=1))
-        assert diff.size == 0, f"{name} differs in rows {diff[:8]}: gpu {g[diff[:2]]} want {w[diff[:2]]}"
-
-
-def around(got, before, after, inplace, slot, room, seeds):
-    """What tt_eval must show around a call, and the closed rows."""
-    hcv0, scv0, feas0, pen0 = before
-    hcv1, scv1, feas1, pen1 = after
-    assert np.array_equal(hcv1, hcv0) and np.array_equal(feas1, feas0)
-    assert np.array_equal(scv1, scv0 - got[3]) and (got[3] >= 0).all()
-    assert np.array_equal(inplace[0], scv1) and np.array_equal(inplace[1], pen1)      # in place = a fresh tt_eval
-    closed = hcv0 != 0
-    assert np.array_equal(got[0][closed], slot[closed]) and np.array_equal(got[1][closed], room[closed])
-    assert np.array_equal(got[2][closed], seeds[closed])
-    for k in range(3, 9):
-        assert not got[k][closed].any(), NAMES[k]
+def around(got, want, before, after, inplace, slot, room, seeds, steps):
+    """walk_checks.check_rows, and the winner: the lowest walker of the largest gain."""
+    closed = wc.check_rows(got, want, before, after, inplace, slot, room, seeds, steps)
     K = got[8].shape[1]
     assert (got[7] >= 0).all() and (got[7] < K).all()
     assert np.array_equal(got[3], got[8].max(axis=1)) and np.array_equal(got[7], got[8].argmax(axis=1))
@@ -104,8 +86,7 @@ def test_rows_vs_model(problems, cid):
     slot, room, seeds = mm.case_rows(cid, inst, model)
     want = model.lahc_multi_rows(slot, room, seeds, K, steps, L, p_swap, p_kempe, 0, rule)
     got, before, after, inplace = run(dp, slot, room, seeds, K, steps, L, p_swap, p_kempe, 0, rule)
-    same(got, want)
-    closed = around(got, before, after, inplace, slot, room, seeds)
+    closed = around(got, want, before, after, inplace, slot, room, seeds, steps)
     print(cid, "walked", int((~closed).sum()), "of", P, "winner", got[7].tolist(), "gain", got[3].tolist(),
           "walker 0", got[8][:, 0].tolist())
     SEEN["cases"] += 1
@@ -116,12 +97,7 @@ def test_rows_vs_model(problems, cid):
         return
     # both kinds of rows in the launch (population spoils rows 2, 7, ...: none among syn_sparse's two)
     assert (~closed).any() and (closed.any() or inst.E < 2 or P <= 2)
-    from ttga.rng import step
-    i = int(np.flatnonzero(~closed)[0])                              # exactly 3 * steps * K draws
-    s = int(seeds[i])
-    for _ in range(3 * steps * K):
-        s = step(s)
-    assert got[2][i] == s
+    i = wc.check_stream_advance(got, seeds, closed, 3 * steps * K)   # exactly 3 * steps * K draws a searched row
     if cid == "sm":
         assert i == 0 and seeds[0] == 2 ** 40 + 7 and got[3][0] > 0  # the state out of range walks, and is row 0
     if cid == "sm-plain":
@@ -186,8 +162,7 @@ def test_equals_chained_calls_of_the_walk(problems, med_rows, P, K):
     seeds = med_rows[2][take] + 104729 * (np.arange(P) // 33)
     want, scv_want, pen_want, hcv0 = chained(dp, slot, room, seeds, K, steps, L, p_swap, p_kempe, rule)
     got, before, after, inplace = run(dp, slot, room, seeds, K, steps, L, p_swap, p_kempe, 0, rule)
-    same(got, want)
-    closed = around(got, before, after, inplace, slot, room, seeds)
+    closed = around(got, want, before, after, inplace, slot, room, seeds, steps)
     assert np.array_equal(inplace[0], scv_want) and np.array_equal(inplace[1], pen_want)
     assert np.array_equal(closed, hcv0 != 0) and not closed[0] and got[3][0] > 0
     print(P, K, "later winners", int((got[7] > 0).sum()), "gain", int(got[3].sum()), "walker 0", int(got[8][:, 0].sum()))
@@ -233,7 +208,7 @@ def test_one_walker_is_the_older_call(problems, older):
     assert np.array_equal(inplace[0], want[6]) and np.array_equal(inplace[1], want[7])       # scv and penalty in place
     assert np.array_equal(got[6][:, :width], host(stats)[:, :width]) and not got[6][:, width:].any()
     assert not got[7].any() and np.array_equal(got[8][:, 0], got[3]) and got[3].sum() > 0
-    around(got, before, after, inplace, slot, room, seeds)
+    around(got, None, before, after, inplace, slot, room, seeds, steps)
 
 
 # ---------------------------------------------------------------- edges
@@ -243,8 +218,7 @@ def test_steps_0_and_1(problems, steps):
     slot, room, seeds = lm.population(inst, 9, model)
     want = model.lahc_multi_rows(slot, room, seeds, 4, steps, 50, 0.25, 0.5)
     got, before, after, inplace = run(dp, slot, room, seeds, 4, steps, 50, 0.25, 0.5)
-    same(got, want)
-    closed = around(got, before, after, inplace, slot, room, seeds)
+    closed = around(got, want, before, after, inplace, slot, room, seeds, steps)
     if steps == 0:                                                   # changes nothing
         assert np.array_equal(got[0], slot) and np.array_equal(got[1], room) and np.array_equal(got[2], seeds)
         assert not any(got[k].any() for k in range(3, 9))
@@ -253,24 +227,9 @@ def test_steps_0_and_1(problems, steps):
 
 
 def test_invalid_genes():
-    """Rows with slot gene 45 / room gene R between valid ones: untouched, rng
-    included, outputs 0, status bit 8; their neighbours walk as the model has
-    them. Own handle: the status word is sticky."""
-    inst = lm.SHAPES["sm"]()
-    dp, model = native.DeviceProblem(inst), mm.Model(inst)
-    slot, room, seeds = lm.population(inst, 6, model)
-    slot[1, 7] = 45
-    room[4, 3] = inst.R
-    assert dp.status() == 0
-    want = model.lahc_multi_rows(slot, room, seeds, 3, 300, 50, 0.25, 0.5)
-    got, _, _, _ = run(dp, slot, room, seeds, 3, 300, 50, 0.25, 0.5, with_eval=False)
-    same(got, want)
-    for i in (1, 2, 4):                                              # row 2 is spoiled: closed too, no status bit for it
-        assert np.array_equal(got[0][i], slot[i]) and np.array_equal(got[1][i], room[i]) and got[2][i] == seeds[i]
-        assert not any(np.asarray(got[k][i]).any() for k in range(3, 9))
-    assert got[4][0] > 0 and got[4][3] > 0 and got[4][5] > 0
-    assert dp.status() & BAD_GENE == BAD_GENE
-    dp.close()
+    """walk_checks.invalid_genes; row 2 is spoiled: closed too, no status bit for it."""
+    a = dict(K=3, steps=300, history=50, p_swap=0.25, p_kempe=0.5)
+    wc.invalid_genes(mm.Model, call, rows, a, 7, closed=(1, 2, 4), winner=(), walker_gain=(3,))
 
 
 def test_all_rows_closed_and_no_status_bit_for_hcv():
@@ -403,13 +362,8 @@ def test_two_streams_two_work_buffers(problems):
 
 
 # ---------------------------------------------------------------- Island
-def run_island(dp, gens=6, **kw):
-    isl = Island(dp, pop_size=10, children=kw.pop("children", 2), max_steps=50, seed=31, init="greedy", **kw)
-    isl.initialize()
-    for _ in range(gens):
-        isl.step()
-    isl.flush()
-    return isl
+def walkers_island(dp, **kw):
+    return run_island(dp, **{**dict(gens=6, children=2, init="greedy"), **kw})
 
 
 @pytest.mark.parametrize("variant", ["plain", "augment", "staggered"])
@@ -417,8 +371,8 @@ def test_island_walkers(problems, variant):
     inst, dp, _ = problems("sm")
     kw = {"plain": {}, "augment": dict(lahc_swap=0.25, lahc_kempe=0.5, lahc_kempe_rooms="augment"),
           "staggered": dict(schedule="staggered", parts=2, children=4, lahc_swap=0.25, lahc_kempe=0.5)}[variant]
-    a = run_island(dp, lahc=200, lahc_walkers=4, **kw)
-    b = run_island(dp, lahc=200, lahc_walkers=4, **kw)
+    a = walkers_island(dp, lahc=200, lahc_walkers=4, **kw)
+    b = walkers_island(dp, lahc=200, lahc_walkers=4, **kw)
     for k in a.pop:
         assert np.array_equal(host(a.pop[k]), host(b.pop[k])), k           # run twice: identical
     p = a.pop
@@ -442,12 +396,12 @@ def test_island_walkers(problems, variant):
 def test_island_one_walker_issues_the_calls_of_today(problems, monkeypatch):
     inst, dp, _ = problems("sm")
     kw = dict(lahc=100, lahc_swap=0.25, lahc_kempe=0.5, lahc_kempe_rooms="augment")
-    today = run_island(dp, **kw)
+    today = walkers_island(dp, **kw)
 
     def boom(*a, **k):
         raise AssertionError("lahc_multi called with Island(lahc_walkers=1)")
     monkeypatch.setattr(dp, "lahc_multi", boom)
-    one = run_island(dp, lahc_walkers=1, **kw)
+    one = walkers_island(dp, lahc_walkers=1, **kw)
     for k in today.pop:
         assert np.array_equal(host(one.pop[k]), host(today.pop[k])), k
     assert one.lahc_stats() == today.lahc_stats() and one.lahc_kempe_stats() == today.lahc_kempe_stats()
@@ -459,44 +413,21 @@ def test_island_one_walker_issues_the_calls_of_today(problems, monkeypatch):
 
 
 # ---------------------------------------------------------------- the drivers
-def _run(cmd, cwd):
-    env = dict(os.environ, PYTHONPATH=str(PKG))
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=str(cwd))
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r
-
-
-def _lines(text, key):
-    return [ln for ln in text.splitlines() if ln.startswith('{"%s"' % key)]
-
-
 def test_walkers_in_both_drivers(tmp_path):
     tim = REPO / "tests" / "golden" / "sm.tim"
     inst = ttga.read_tim(tim)
-    exe = PKG / "ttga-ga"
-    assert exe.exists(), "ttga-ga not built (make -C timetabling-ga-mpi-openmp_amd)"
     base = ["-i", str(tim), "-s", "29", "-p", "1", "--pop", "16", "--children", "8", "--generations", "10",
             "--init", "greedy"]
-    flags = ["--lahc", "200", "--lahc-walkers", "4"]
-    py = _run([sys.executable, "-m", "ttga.islands", *base, *flags], tmp_path)
-    cc = _run([str(exe), *flags, *base], tmp_path)
-    a, b = json_lines(py.stdout), json_lines(cc.stdout)
-    assert a == b and a
-    assert _lines(py.stdout, "lahcWalkers") == _lines(cc.stdout, "lahcWalkers")           # byte for byte
-    assert _lines(py.stdout, "lahc") == _lines(cc.stdout, "lahc")
-    lines = [x["lahcWalkers"] for x in a if "lahcWalkers" in x]
+    py, cc, a, lines = both_drivers(tmp_path, base, ["--lahc", "200", "--lahc-walkers", "4"], "lahcWalkers", inst)
+    assert stage_lines(py.stdout, "lahc") == stage_lines(cc.stdout, "lahc")              # byte for byte
     assert len(lines) == 1
     k = lines[0]
     assert set(k) == {"rows", "walkers", "gain", "gainFirst", "winnerLater"} and k["walkers"] == 4
     assert k["gain"] >= k["gainFirst"] > 0 and 0 < k["winnerLater"] <= k["rows"]
     walk = [x["lahc"] for x in a if "lahc" in x][0]
     assert walk["gain"] == k["gain"] and walk["searched"] == k["rows"]
-    from ttga.validate import check_text
-    for r_ in (py, cc):
-        reps = check_text(inst, r_.stdout)
-        assert reps and all(x["ok"] for x in reps), reps
     # without the flag (the Python driver) and with one walker (the native one): no such line, the same output
-    plain_py = _run([sys.executable, "-m", "ttga.islands", *base, "--lahc", "200"], tmp_path)
-    plain_cc = _run([str(exe), "--lahc", "200", "--lahc-walkers", "1", *base], tmp_path)
-    assert not _lines(plain_py.stdout, "lahcWalkers") and not _lines(plain_cc.stdout, "lahcWalkers")
+    plain_py = run_driver([sys.executable, "-m", "ttga.islands", *base, "--lahc", "200"], tmp_path)
+    plain_cc = run_driver([str(GA), "--lahc", "200", "--lahc-walkers", "1", *base], tmp_path)
+    assert not stage_lines(plain_py.stdout, "lahcWalkers") and not stage_lines(plain_cc.stdout, "lahcWalkers")
     assert json_lines(plain_py.stdout) == json_lines(plain_cc.stdout)

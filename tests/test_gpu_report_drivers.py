@@ -1,7 +1,6 @@
 """--report in both GA drivers (python -m ttga.islands, ttga-ga): the same
 report lines from both, nothing else changed in the output, and the best
 member's parts reproduce the solution line."""
-import os
 import pathlib
 import subprocess
 import sys
@@ -10,6 +9,7 @@ import pytest
 
 import ttga
 from helpers import json_lines as _json_lines
+from stage_checks import run_driver
 from ttga import native, validate
 
 pytestmark = pytest.mark.gpu
@@ -23,13 +23,6 @@ def _raw_report_lines(text):
     return [ln for ln in text.splitlines() if ln.startswith('{"report"')]
 
 
-def _run(cmd, cwd):
-    env = dict(os.environ, PYTHONPATH=str(PKG))
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=str(cwd))
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r
-
-
 @pytest.mark.parametrize("extra", [[], ["--stagger"]], ids=["batch", "stagger"])
 def test_report_lines_of_both_drivers(tmp_path, extra):
     inst = ttga.config_instance("sm")
@@ -38,9 +31,9 @@ def test_report_lines_of_both_drivers(tmp_path, extra):
     exe = PKG / "ttga-ga"
     assert exe.exists(), "ttga-ga not built (make -C timetabling-ga-mpi-openmp_amd)"
     base = ["-i", str(tim), "-s", "42", "-p", "1", "-c", "3", "--generations", "120", "--pop", "12", *extra]
-    py = _run([sys.executable, "-m", "ttga.islands", *base, "--report"], tmp_path)
-    cc = _run([str(exe), "--report", *base], tmp_path)
-    plain = _run([str(exe), *base], tmp_path)
+    py = run_driver([sys.executable, "-m", "ttga.islands", *base, "--report"], tmp_path)
+    cc = run_driver([str(exe), "--report", *base], tmp_path)
+    plain = run_driver([str(exe), *base], tmp_path)
 
     # the report lines are the same bytes from both drivers; the rest of the output is
     # the run without the flag

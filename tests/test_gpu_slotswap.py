@@ -4,26 +4,18 @@ around every call tt_eval and tt_eval_parts: hcv, feasibility and the three
 hard parts unchanged, scv lower by exactly the gain, and the scv / penalty
 updated in place equal to a fresh evaluation. Then Island(slot_swap=...) and
 the two drivers with --slot-swap."""
-import os
-import pathlib
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import ttga
 import slotswap_model as sm
 from helpers import dev, host, json_lines
+from stage_checks import GA, both_drivers, run_driver, run_island
 
 pytestmark = pytest.mark.gpu
 
 import torch  # noqa: E402
 from ttga import native  # noqa: E402
-from ttga.ga import Island  # noqa: E402
-
-REPO = pathlib.Path(__file__).resolve().parent.parent
-PKG = REPO / "timetabling-ga-mpi-openmp_amd"
 
 UNCAPPED = 2 ** 31 - 1
 # tt_device_status bits 0 and 2..7 (bit 1 is the local search's): clear unless a test says otherwise
@@ -237,23 +229,14 @@ def test_limit():
 
 
 # ---------------------------------------------------------------- Island
-def run_island(dp, gens=5, **kw):
-    isl = Island(dp, pop_size=10, children=4, max_steps=50, seed=31, **kw)
-    isl.initialize()
-    for _ in range(gens):
-        isl.step()
-    isl.flush()
-    return isl
-
-
 def test_island_slot_swap_0_issues_no_call(problems, monkeypatch):
     inst, dp = problems("sm")
-    plain = run_island(dp)
+    plain = run_island(dp, gens=5, children=4)
 
     def boom(*a, **k):
         raise AssertionError("slot_swap called with Island(slot_swap=0)")
     monkeypatch.setattr(dp, "slot_swap", boom)
-    off = run_island(dp, slot_swap=0)
+    off = run_island(dp, gens=5, children=4, slot_swap=0)
     for k in plain.pop:
         assert np.array_equal(host(off.pop[k]), host(plain.pop[k])), k
     with pytest.raises(ValueError, match="slot_swap_stats"):
@@ -265,7 +248,7 @@ def test_island_slot_swap_0_issues_no_call(problems, monkeypatch):
 @pytest.mark.parametrize("schedule", ["batch", "staggered"])
 def test_island_slot_swap(problems, schedule):
     inst, dp = problems("sm")
-    isl = run_island(dp, slot_swap=4, schedule=schedule, parts=2)
+    isl = run_island(dp, gens=5, children=4, slot_swap=4, schedule=schedule, parts=2)
     p = isl.pop
     hcv, scv, feas, pen = (host(t) for t in dp.eval(p["slot"], p["room"]))
     assert np.array_equal(host(p["hcv"]), hcv) and np.array_equal(host(p["scv"]), scv)
@@ -282,33 +265,14 @@ def test_island_slot_swap(problems, schedule):
 
 
 # ---------------------------------------------------------------- the drivers
-def _run(cmd, cwd):
-    env = dict(os.environ, PYTHONPATH=str(PKG))
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=str(cwd))
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r
-
-
 def test_slot_swap_in_both_drivers(tmp_path, problems):
     inst = problems("sm")[0]
     tim = tmp_path / "sm.tim"
     ttga.write_tim(inst, tim)
-    exe = PKG / "ttga-ga"
-    assert exe.exists(), "ttga-ga not built (make -C timetabling-ga-mpi-openmp_amd)"
     base = ["-i", str(tim), "-s", "29", "-p", "1", "--pop", "16", "--children", "8", "--generations", "10"]
-    py = _run([sys.executable, "-m", "ttga.islands", *base, "--slot-swap", "4"], tmp_path)
-    cc = _run([str(exe), "--slot-swap", "4", *base], tmp_path)
-    cc_zero = _run([str(exe), *base, "--slot-swap", "0"], tmp_path)
-    a, b = json_lines(py.stdout), json_lines(cc.stdout)
-    assert a == b and a
-    lines = [x["slotSwap"] for x in a if "slotSwap" in x]
+    py, cc, a, lines = both_drivers(tmp_path, base, ["--slot-swap", "4"], "slotSwap", inst)
+    cc_zero = run_driver([str(GA), *base, "--slot-swap", "0"], tmp_path)
     assert len(lines) == 1 and set(lines[0]) == {"gain", "improved", "meanPasses", "rows"}
     k = lines[0]
     assert k["rows"] == 16 + 80 and 0 < k["improved"] <= k["rows"] and 1 <= k["meanPasses"] <= 4 and k["gain"] > 0
-    kinds = [next(iter(x)) for x in a]
-    assert kinds.index("slotSwap") > kinds.index("solution")
     assert not any("slotSwap" in x for x in json_lines(cc_zero.stdout))            # 0: no call, no line
-    from ttga.validate import check_text
-    for r_ in (py, cc):
-        reps = check_text(inst, r_.stdout)
-        assert reps and all(x["ok"] for x in reps), reps

@@ -7,9 +7,6 @@ over whole generations in both schedules, and --unique in both drivers.
 The expected values share no code with the kernels: the first occurrences come
 from numpy.unique over the concatenated rows, the keep rule from those, the
 replacement from the oracle's ga_replace with the kept children."""
-import os
-import pathlib
-import subprocess
 import sys
 
 import numpy as np
@@ -18,14 +15,13 @@ import pytest
 import ttga
 from helpers import dev, host, json_lines as _json_lines, oracle_population
 from oracle_lib import oracle
+from stage_checks import GA, both_drivers, run_driver, stage_lines
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 from ttga import native  # noqa: E402
 from ttga.ga import Island, stream_seeds  # noqa: E402
 
-REPO = pathlib.Path(__file__).resolve().parent.parent
-PKG = REPO / "timetabling-ga-mpi-openmp_amd"
 KEYS = ("slot", "room", "hcv", "scv", "feasible", "penalty")
 
 
@@ -411,28 +407,16 @@ def test_island_unique_equals_plain_when_nothing_is_dropped(sm):
 
 
 # ---------------------------------------------------------------- the drivers
-def _run(cmd, cwd):
-    env = dict(os.environ, PYTHONPATH=str(PKG))
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=str(cwd))
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r
-
-
 def test_unique_lines_of_both_drivers(tmp_path, sm):
     inst, dp, o = sm
     tim = tmp_path / "sm.tim"
     ttga.write_tim(inst, tim)
-    exe = PKG / "ttga-ga"
-    assert exe.exists(), "ttga-ga not built (make -C timetabling-ga-mpi-openmp_amd)"
     base = ["-i", str(tim), "-s", "29", "-p", "1", "--pop", "32", "--children", "32", "--generations", "12"]
-    py = _run([sys.executable, "-m", "ttga.islands", *base, "--unique"], tmp_path)
-    cc = _run([str(exe), "--unique", *base], tmp_path)
-    py_plain = _run([sys.executable, "-m", "ttga.islands", *base], tmp_path)
-    cc_plain = _run([str(exe), *base], tmp_path)
-    raw = [[ln for ln in r.stdout.splitlines() if ln.startswith('{"unique"')] for r in (py, cc, py_plain, cc_plain)]
+    py, cc, b, _ = both_drivers(tmp_path, base, ["--unique"], "unique", inst)
+    py_plain = run_driver([sys.executable, "-m", "ttga.islands", *base], tmp_path)
+    cc_plain = run_driver([str(GA), *base], tmp_path)
+    raw = [stage_lines(r.stdout, "unique") for r in (py, cc, py_plain, cc_plain)]
     assert raw[0] == raw[1] and len(raw[0]) == 1 and raw[2] == [] and raw[3] == []
-    a, b = _json_lines(py.stdout), _json_lines(cc.stdout)
-    assert a == b
     assert _json_lines(py_plain.stdout) == _json_lines(cc_plain.stdout)
     u = [x["unique"] for x in b if "unique" in x][0]
     # the run is the model's (32, 32, 12) at the island's seed (ga.cpp:412 leaves island 0's as given)
@@ -441,12 +425,9 @@ def test_unique_lines_of_both_drivers(tmp_path, sm):
     assert u["dropped"] > 0
     keys = [next(iter(x)) for x in b]
     assert keys.index("unique") == keys.index("solution") + 1 and keys[-1] == "runEntry"
-    both = _json_lines(_run([str(exe), "--unique", "--report", *base], tmp_path).stdout)
+    both = _json_lines(run_driver([str(GA), "--unique", "--report", *base], tmp_path).stdout)
     keys = [next(iter(x)) for x in both]
     assert keys.index("unique") == keys.index("solution") + 1 and keys.index("report") == keys.index("unique") + 1
-    from ttga.validate import check_text
-    reps = check_text(inst, cc.stdout)
-    assert reps and all(r["ok"] for r in reps), reps
 
 
 def test_unique_lines_of_both_drivers_two_islands(tmp_path, sm):
@@ -457,12 +438,11 @@ def test_unique_lines_of_both_drivers_two_islands(tmp_path, sm):
     inst, dp, o = sm
     tim = tmp_path / "sm.tim"
     ttga.write_tim(inst, tim)
-    exe = PKG / "ttga-ga"
     base = ["-i", str(tim), "-s", "29", "-p", "1", "--pop", "32", "--children", "32", "--generations", "12",
             "--islands", "2", "--unique"]
-    py = _run([sys.executable, "-m", "ttga.islands", *base], tmp_path)
-    cc = _run([str(exe), *base], tmp_path)
-    raw = [[ln for ln in r.stdout.splitlines() if ln.startswith('{"unique"')] for r in (py, cc)]
+    py = run_driver([sys.executable, "-m", "ttga.islands", *base], tmp_path)
+    cc = run_driver([str(GA), *base], tmp_path)
+    raw = [stage_lines(r.stdout, "unique") for r in (py, cc)]
     assert raw[0] == raw[1] and len(raw[0]) == 2
     got = [x["unique"] for x in _json_lines(cc.stdout) if "unique" in x]
     for k in (0, 1):

@@ -6,9 +6,7 @@ the Control-style parse, Island's check of `init`, and the numpy model
 prototype's figures on comp01."""
 import ctypes
 import pathlib
-import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,48 +14,27 @@ import pytest
 import ttga
 import greedy_model as gm
 from oracle_lib import ORACLE_PATH, oracle
+from stage_checks import (Sink, build_and_run_consumer, check_exports, rejected_by_native_driver,
+                          rejected_by_parse_control, stripped_before_pair_count)
 from ttga import native
 from ttga.ga import Island
 from ttga.islands import parse_control
 
 REPO = pathlib.Path(__file__).resolve().parent.parent
-PKG = REPO / "timetabling-ga-mpi-openmp_amd"
 HEADER = REPO / "include" / "ttga_greedy.h"
 CONSUMER = REPO / "tests" / "boundary_greedy_cxx98.cpp"
 
 
-def header_symbols():
-    return set(re.findall(r"\b(tt_[a-z_0-9]+)\s*\(", HEADER.read_text().split("#ifndef TTGA_GREEDY_H")[1]))
-
-
 def test_header_symbols_are_exported_listed_and_called():
-    syms = header_symbols()
-    assert syms == {"tt_greedy_work_bytes", "tt_greedy_order", "tt_greedy_init"}
-    assert syms == set(native.GREEDY_EXPORTS)
-    for other in (native.EXPORTS, native.REPORT_EXPORTS, native.UNIQUE_EXPORTS):
-        assert not syms & set(other)
-    lib = native.load()
-    for s in syms:
-        assert hasattr(lib, s), s
-    called = set(re.findall(r"\b(tt_[a-z_0-9]+)\s*\(", CONSUMER.read_text()))
-    assert syms <= called, sorted(syms - called)
+    check_exports(HEADER, "TTGA_GREEDY_H", "GREEDY_EXPORTS", CONSUMER,
+                  {"tt_greedy_work_bytes", "tt_greedy_order", "tt_greedy_init"})
     assert '#include "ttga.h"' in HEADER.read_text()
     assert "ttga_greedy.h" in (REPO / "include" / "ttga.h").read_text()
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_cxx98_greedy_consumer_builds_and_links(tmp_path):
-    exe = tmp_path / "consumer"
-    r = subprocess.run(["g++", "-Wall", "-ansi", "-O3", "-pedantic", "-Werror", "-I", str(REPO / "include"),
-                        str(CONSUMER), "-L", str(PKG), "-lttga", f"-Wl,-rpath,{PKG}", "-o", str(exe)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0 and r.stderr == "", r.stderr
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert run.returncode in (0, 2), run.stdout + run.stderr
-    if run.returncode == 2:
-        assert "TT_ERR_DEVICE" in run.stdout and "null-handle checks: 0 wrong" in run.stdout
-    else:
-        assert "null-buffer checks: 0 wrong" in run.stdout
+    build_and_run_consumer(CONSUMER, tmp_path)
 
 
 def test_argument_errors_without_a_device():
@@ -87,14 +64,6 @@ def test_argument_errors_without_a_device():
     assert lib.tt_greedy_init(fake, buf, buf, buf, buf, 0, None) == native.TT_OK        # no launch
 
 
-class Sink:
-    def __init__(self):
-        self.text = ""
-
-    def write(self, s):
-        self.text += s
-
-
 def test_init_flag_in_the_control_parse():
     ctl = parse_control(["-i", "x.tim", "--init", "greedy", "-s", "42"], out=Sink(), err=Sink())
     assert ctl["init"] == "greedy" and ctl["seed"] == 42 and ctl["input"] == "x.tim"
@@ -103,21 +72,13 @@ def test_init_flag_in_the_control_parse():
     both = parse_control(["--unique", "-i", "x.tim", "--init", "greedy", "--pop", "20"], out=Sink(), err=Sink())
     assert both["init"] == "greedy" and both["unique"] is True and both["pop"] == 20
     for bad in (["-i", "x.tim", "--init", "best"], ["-i", "x.tim", "--init"]):
-        err = Sink()
-        with pytest.raises(SystemExit) as ex:
-            parse_control(bad, out=Sink(), err=err)
-        assert ex.value.code == 1 and "--init must be random or greedy" in err.text
+        rejected_by_parse_control(bad, "--init must be random or greedy", exact=True)
 
 
 def test_init_flag_in_the_native_driver():
-    exe = PKG / "ttga-ga"
-    assert exe.exists(), "ttga-ga not built (make -C timetabling-ga-mpi-openmp_amd)"
     for bad in (["-i", "x.tim", "--init", "best"], ["-i", "x.tim", "--init"]):
-        r = subprocess.run([str(exe), *bad], capture_output=True, text=True, timeout=60)
-        assert r.returncode == 1 and "--init must be random or greedy" in r.stderr
-    # the flag and its value are stripped before the pair count
-    r = subprocess.run([str(exe), "--init", "greedy", "-s"], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 1 and "Parse error: Number of command line parameters incorrect" in r.stderr
+        rejected_by_native_driver(bad, "--init must be random or greedy", exact=True)
+    stripped_before_pair_count(["--init", "greedy"])
 
 
 def test_island_rejects_a_bad_init_before_any_device_call():

@@ -6,15 +6,15 @@ and the numpy model (tests/kempe_model.py) against an independent union-find
 and against ttga.validate's correlated-pairs count."""
 import ctypes
 import pathlib
-import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import ttga
 import kempe_model as km
+from stage_checks import (Sink, build_and_run_consumer, check_exports, rejected_by_native_driver,
+                          rejected_by_parse_control, stripped_before_pair_count)
 from ttga import native
 from ttga.ga import Island, kempe_line
 from ttga.islands import parse_control
@@ -22,26 +22,12 @@ from ttga.rng import ParkMiller
 from ttga.validate import evaluate
 
 REPO = pathlib.Path(__file__).resolve().parent.parent
-PKG = REPO / "timetabling-ga-mpi-openmp_amd"
 HEADER = REPO / "include" / "ttga_kempe.h"
 CONSUMER = REPO / "tests" / "boundary_kempe_cxx98.cpp"
 
 
-def header_symbols():
-    return set(re.findall(r"\b(tt_[a-z_0-9]+)\s*\(", HEADER.read_text().split("#ifndef TTGA_KEMPE_H")[1]))
-
-
 def test_header_symbols_are_exported_listed_and_called():
-    syms = header_symbols()
-    assert syms == {"tt_kempe_move"}
-    assert syms == set(native.KEMPE_EXPORTS)
-    for other in (native.EXPORTS, native.REPORT_EXPORTS, native.UNIQUE_EXPORTS, native.GREEDY_EXPORTS):
-        assert not syms & set(other)
-    lib = native.load()
-    for s in syms:
-        assert hasattr(lib, s), s
-    called = set(re.findall(r"\b(tt_[a-z_0-9]+)\s*\(", CONSUMER.read_text()))
-    assert syms <= called, sorted(syms - called)
+    check_exports(HEADER, "TTGA_KEMPE_H", "KEMPE_EXPORTS", CONSUMER, {"tt_kempe_move"})
     assert '#include "ttga.h"' in HEADER.read_text()
     top = (REPO / "include" / "ttga.h").read_text()
     assert "ttga_kempe.h" in top and "bit 6 (64)" in top
@@ -49,17 +35,7 @@ def test_header_symbols_are_exported_listed_and_called():
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_cxx98_kempe_consumer_builds_and_links(tmp_path):
-    exe = tmp_path / "consumer"
-    r = subprocess.run(["g++", "-Wall", "-ansi", "-O3", "-pedantic", "-Werror", "-I", str(REPO / "include"),
-                        str(CONSUMER), "-L", str(PKG), "-lttga", f"-Wl,-rpath,{PKG}", "-o", str(exe)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0 and r.stderr == "", r.stderr
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert run.returncode in (0, 2), run.stdout + run.stderr
-    if run.returncode == 2:
-        assert "TT_ERR_DEVICE" in run.stdout and "null-handle checks: 0 wrong" in run.stdout
-    else:
-        assert "null-buffer checks: 0 wrong" in run.stdout
+    build_and_run_consumer(CONSUMER, tmp_path)
 
 
 def test_argument_errors_without_a_device():
@@ -92,12 +68,7 @@ def test_argument_errors_without_a_device():
         assert lib.tt_kempe_move(fake, buf, buf, buf, 0, prob, 7, None, None) == native.TT_OK
 
 
-class Sink:
-    def __init__(self):
-        self.text = ""
-
-    def write(self, s):
-        self.text += s
+MESSAGE = "--kempe must be a probability in [0, 1], --kempe-max-chain an integer >= 0"
 
 
 def test_kempe_flags_in_the_control_parse():
@@ -113,23 +84,14 @@ def test_kempe_flags_in_the_control_parse():
     for bad in (["-i", "x.tim", "--kempe", "1.5"], ["-i", "x.tim", "--kempe", "-0.1"], ["-i", "x.tim", "--kempe"],
                 ["-i", "x.tim", "--kempe", "nan"], ["-i", "x.tim", "--kempe", "half"],
                 ["-i", "x.tim", "--kempe-max-chain", "-1"], ["-i", "x.tim", "--kempe-max-chain"]):
-        err = Sink()
-        with pytest.raises(SystemExit) as ex:
-            parse_control(bad, out=Sink(), err=err)
-        assert ex.value.code == 1 and "--kempe must be a probability" in err.text
+        rejected_by_parse_control(bad, MESSAGE, exact=True)
 
 
 def test_kempe_flags_in_the_native_driver():
-    exe = PKG / "ttga-ga"
-    assert exe.exists(), "ttga-ga not built (make -C timetabling-ga-mpi-openmp_amd)"
     for bad in (["-i", "x.tim", "--kempe", "1.5"], ["-i", "x.tim", "--kempe"], ["-i", "x.tim", "--kempe", "nan"],
                 ["-i", "x.tim", "--kempe", "half"], ["-i", "x.tim", "--kempe-max-chain", "-1"]):
-        r = subprocess.run([str(exe), *bad], capture_output=True, text=True, timeout=60)
-        assert r.returncode == 1 and "--kempe must be a probability" in r.stderr
-    # the flags and their values are stripped before the pair count
-    r = subprocess.run([str(exe), "--kempe", "0.5", "--kempe-max-chain", "4", "-s"], capture_output=True, text=True,
-                       timeout=60)
-    assert r.returncode == 1 and "Parse error: Number of command line parameters incorrect" in r.stderr
+        rejected_by_native_driver(bad, MESSAGE, exact=True)
+    stripped_before_pair_count(["--kempe", "0.5", "--kempe-max-chain", "4"])
 
 
 def test_island_rejects_bad_kempe_values_before_any_device_call():

@@ -7,15 +7,15 @@ call, the --lahc flags in both drivers' parse, Island's argument checks and
 the lahc line."""
 import ctypes
 import pathlib
-import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import ttga
 import lahc_model as lm
+from stage_checks import (Sink, build_and_run_consumer, check_exports, rejected_by_native_driver,
+                          rejected_by_parse_control, stripped_before_pair_count)
 from ttga import native
 from ttga.ga import Island, lahc_line
 from ttga.islands import parse_control
@@ -23,7 +23,6 @@ from ttga.rng import ParkMiller
 from ttga.validate import evaluate
 
 REPO = pathlib.Path(__file__).resolve().parent.parent
-PKG = REPO / "timetabling-ga-mpi-openmp_amd"
 HEADER = REPO / "include" / "ttga_lahc.h"
 CONSUMER = REPO / "tests" / "boundary_lahc_cxx98.cpp"
 
@@ -163,22 +162,8 @@ def test_model_hcv_is_the_validators():
 
 
 # ---------------------------------------------------------------- the boundary
-def header_symbols():
-    return set(re.findall(r"\b(tt_[a-z_0-9]+)\s*\(", HEADER.read_text().split("#ifndef TTGA_LAHC_H")[1]))
-
-
 def test_header_symbols_are_exported_listed_and_called():
-    syms = header_symbols()
-    assert syms == {"tt_lahc"}
-    assert syms == set(native.LAHC_EXPORTS)
-    for other in (native.EXPORTS, native.REPORT_EXPORTS, native.UNIQUE_EXPORTS, native.GREEDY_EXPORTS,
-                  native.KEMPE_EXPORTS, native.SLOTSWAP_EXPORTS):
-        assert not syms & set(other)
-    lib = native.load()
-    for s in syms:
-        assert hasattr(lib, s), s
-    called = set(re.findall(r"\b(tt_[a-z_0-9]+)\s*\(", CONSUMER.read_text()))
-    assert syms <= called, sorted(syms - called)
+    check_exports(HEADER, "TTGA_LAHC_H", "LAHC_EXPORTS", CONSUMER, {"tt_lahc"})
     assert '#include "ttga.h"' in HEADER.read_text()
     top = (REPO / "include" / "ttga.h").read_text()
     assert "ttga_lahc.h" in top and "bit 8 (256)" in top
@@ -186,17 +171,7 @@ def test_header_symbols_are_exported_listed_and_called():
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_cxx98_lahc_consumer_builds_and_links(tmp_path):
-    exe = tmp_path / "consumer"
-    r = subprocess.run(["g++", "-Wall", "-ansi", "-O3", "-pedantic", "-Werror", "-I", str(REPO / "include"),
-                        str(CONSUMER), "-L", str(PKG), "-lttga", f"-Wl,-rpath,{PKG}", "-o", str(exe)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0 and r.stderr == "", r.stderr
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert run.returncode in (0, 2), run.stdout + run.stderr
-    if run.returncode == 2:
-        assert "TT_ERR_DEVICE" in run.stdout and "null-handle checks: 0 wrong" in run.stdout
-    else:
-        assert "null-buffer checks: 0 wrong" in run.stdout
+    build_and_run_consumer(CONSUMER, tmp_path)
 
 
 def test_argument_errors_without_a_device():
@@ -232,14 +207,6 @@ def test_argument_errors_without_a_device():
 
 
 # ---------------------------------------------------------------- the flags, Island, the line
-class Sink:
-    def __init__(self):
-        self.text = ""
-
-    def write(self, s):
-        self.text += s
-
-
 BAD_FLAGS = ((["-i", "x.tim", "--lahc", "-1"], "--lahc must be a non-negative integer"),
              (["-i", "x.tim", "--lahc"], "--lahc must be a non-negative integer"),
              (["-i", "x.tim", "--lahc", "2.5"], "--lahc must be a non-negative integer"),
@@ -263,22 +230,13 @@ def test_lahc_flags_in_the_control_parse():
                          err=Sink())
     assert both["slot_swap"] == 1 and both["lahc"] == 2000 and both["unique"] is True and both["pop"] == 20
     for bad, msg in BAD_FLAGS:
-        err = Sink()
-        with pytest.raises(SystemExit) as ex:
-            parse_control(bad, out=Sink(), err=err)
-        assert ex.value.code == 1 and msg in err.text
+        rejected_by_parse_control(bad, msg, exact=True)
 
 
 def test_lahc_flags_in_the_native_driver():
-    exe = PKG / "ttga-ga"
-    assert exe.exists(), "ttga-ga not built (make -C timetabling-ga-mpi-openmp_amd)"
     for bad, msg in BAD_FLAGS:
-        r = subprocess.run([str(exe), *bad], capture_output=True, text=True, timeout=60)
-        assert r.returncode == 1 and msg in r.stderr, (bad, r.stderr)
-    # the flags and their values are stripped before the pair count
-    r = subprocess.run([str(exe), "--lahc", "4", "--lahc-history", "7", "--lahc-swap", "0.5", "-s"], capture_output=True,
-                       text=True, timeout=60)
-    assert r.returncode == 1 and "Parse error: Number of command line parameters incorrect" in r.stderr
+        rejected_by_native_driver(bad, msg, exact=True)
+    stripped_before_pair_count(["--lahc", "4", "--lahc-history", "7", "--lahc-swap", "0.5"])
 
 
 def test_island_checks_its_lahc_arguments_before_any_device_call():

@@ -8,9 +8,7 @@ C++98 consumer sees it, its argument handling before any device call, the
 line."""
 import ctypes
 import pathlib
-import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,6 +16,8 @@ import pytest
 import ttga
 import lahc_kempe_model as km
 import lahc_model as lm
+from stage_checks import (Sink, build_and_run_consumer, check_exports, rejected_by_native_driver,
+                          rejected_by_parse_control, stripped_before_pair_count)
 from ttga import native, stages
 from ttga.ga import Island, lahc_kempe_line
 from ttga.islands import parse_control
@@ -25,7 +25,6 @@ from ttga.rng import ParkMiller
 from ttga.validate import evaluate
 
 REPO = pathlib.Path(__file__).resolve().parent.parent
-PKG = REPO / "timetabling-ga-mpi-openmp_amd"
 HEADER = REPO / "include" / "ttga_lahc_kempe.h"
 CONSUMER = REPO / "tests" / "boundary_lahc_kempe_cxx98.cpp"
 
@@ -197,29 +196,13 @@ def test_the_ascending_order_of_the_room_rule_matters():
 
 # ---------------------------------------------------------------- the boundary
 def test_header_symbol_is_exported_listed_and_called():
-    syms = set(re.findall(r"\b(tt_[a-z_0-9]+)\s*\(", HEADER.read_text().split("#ifndef TTGA_LAHC_KEMPE_H")[1]))
-    assert syms == {"tt_lahc_kempe"} == set(native.LAHC_KEMPE_EXPORTS)
-    for other in (native.EXPORTS, native.REPORT_EXPORTS, native.UNIQUE_EXPORTS, native.GREEDY_EXPORTS,
-                  native.KEMPE_EXPORTS, native.SLOTSWAP_EXPORTS, native.LAHC_EXPORTS, native.CX_EXPORTS):
-        assert not syms & set(other)
-    assert hasattr(native.load(), "tt_lahc_kempe")
-    assert syms <= set(re.findall(r"\b(tt_[a-z_0-9]+)\s*\(", CONSUMER.read_text()))
+    check_exports(HEADER, "TTGA_LAHC_KEMPE_H", "LAHC_KEMPE_EXPORTS", CONSUMER, {"tt_lahc_kempe"})
     assert '#include "ttga_lahc_kempe.h"' in (REPO / "include" / "ttga_lahc.h").read_text()
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_cxx98_consumer_builds_and_links(tmp_path):
-    exe = tmp_path / "consumer"
-    r = subprocess.run(["g++", "-Wall", "-ansi", "-O3", "-pedantic", "-Werror", "-I", str(REPO / "include"),
-                        str(CONSUMER), "-L", str(PKG), "-lttga", f"-Wl,-rpath,{PKG}", "-o", str(exe)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0 and r.stderr == "", r.stderr
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert run.returncode in (0, 2), run.stdout + run.stderr
-    if run.returncode == 2:
-        assert "TT_ERR_DEVICE" in run.stdout and "null-handle checks: 0 wrong" in run.stdout
-    else:
-        assert "null-buffer checks: 0 wrong" in run.stdout
+    build_and_run_consumer(CONSUMER, tmp_path)
 
 
 def test_argument_errors_without_a_device():
@@ -257,14 +240,6 @@ def test_argument_errors_without_a_device():
 
 
 # ---------------------------------------------------------------- the flags, Island, the line
-class Sink:
-    def __init__(self):
-        self.text = ""
-
-    def write(self, s):
-        self.text += s
-
-
 PROB = "--lahc-kempe must be a probability in [0, 1]"
 CHAIN = "--lahc-kempe-max-chain must be a non-negative integer"
 BAD_FLAGS = ((["-i", "x.tim", "--lahc", "10", "--lahc-kempe", "1.5"], PROB),
@@ -297,22 +272,13 @@ def test_flags_in_the_control_parse():
     assert ctl["lahc_kempe"] == 0 and "lahc" not in ctl
     assert "lahc_kempe" not in parse_control(["-i", "x.tim", "--lahc", "5"], out=Sink(), err=Sink())
     for bad, msg in BAD_FLAGS:
-        err = Sink()
-        with pytest.raises(SystemExit) as ex:
-            parse_control(bad, out=Sink(), err=err)
-        assert ex.value.code == 1 and err.text == f"Error: {msg}\n", (bad, err.text)
+        rejected_by_parse_control(bad, msg, exact=True)
 
 
 def test_flags_in_the_native_driver():
-    exe = PKG / "ttga-ga"
-    assert exe.exists(), "ttga-ga not built (make -C timetabling-ga-mpi-openmp_amd)"
     for bad, msg in BAD_FLAGS:
-        r = subprocess.run([str(exe), *bad], capture_output=True, text=True, timeout=60)
-        assert r.returncode == 1 and r.stderr == f"Error: {msg}\n", (bad, r.stderr)
-    # the flags and their values are stripped before the pair count
-    r = subprocess.run([str(exe), "--lahc", "4", "--lahc-kempe", "0.5", "--lahc-kempe-max-chain", "7", "--lahc-swap",
-                        "0.5", "-s"], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 1 and "Parse error: Number of command line parameters incorrect" in r.stderr
+        rejected_by_native_driver(bad, msg, exact=True)
+    stripped_before_pair_count(["--lahc", "4", "--lahc-kempe", "0.5", "--lahc-kempe-max-chain", "7", "--lahc-swap", "0.5"])
 
 
 def test_flags_are_in_the_table_for_the_tools():

@@ -6,9 +6,7 @@ consumer sees it, its argument handling before any device call, --lahc-walkers
 in both drivers' parse, stages.validate, Island and the lahcWalkers line."""
 import ctypes
 import pathlib
-import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,6 +14,8 @@ import pytest
 import lahc_kempe_aug_model as am
 import lahc_model as lm
 import lahc_multi_model as mm
+from stage_checks import (Sink, build_and_run_consumer, check_exports, rejected_by_native_driver,
+                          rejected_by_parse_control, stripped_before_pair_count)
 from ttga import native, stages
 from ttga.ga import Island, lahc_walkers_line
 from ttga.islands import parse_control
@@ -152,15 +152,8 @@ def test_what_the_gpu_cases_must_show():
 
 # ---------------------------------------------------------------- the boundary
 def test_header_symbols_are_exported_listed_and_called():
-    syms = set(re.findall(r"\b(tt_[a-z_0-9]+)\s*\(", HEADER.read_text().split("#ifndef TTGA_LAHC_MULTI_H")[1]))
-    assert syms == {"tt_lahc_multi", "tt_lahc_multi_work_bytes"} == set(native.LAHC_MULTI_EXPORTS)
-    for other in (native.EXPORTS, native.REPORT_EXPORTS, native.UNIQUE_EXPORTS, native.GREEDY_EXPORTS,
-                  native.KEMPE_EXPORTS, native.SLOTSWAP_EXPORTS, native.LAHC_EXPORTS, native.LAHC_KEMPE_EXPORTS,
-                  native.LAHC_KEMPE_AUG_EXPORTS, native.CX_EXPORTS):
-        assert not syms & set(other)
-    lib = native.load()
-    assert hasattr(lib, "tt_lahc_multi") and hasattr(lib, "tt_lahc_multi_work_bytes")
-    assert syms <= set(re.findall(r"\b(tt_[a-z_0-9]+)\s*\(", CONSUMER.read_text()))
+    check_exports(HEADER, "TTGA_LAHC_MULTI_H", "LAHC_MULTI_EXPORTS", CONSUMER,
+                  {"tt_lahc_multi", "tt_lahc_multi_work_bytes"})
     text = (REPO / "include" / "ttga_lahc.h").read_text()
     assert text.index('#include "ttga_lahc_kempe_aug.h"') < text.index('#include "ttga_lahc_multi.h"')
     assert "1,552" in HEADER.read_text() and native.MAX_WALKERS == 1024
@@ -168,17 +161,7 @@ def test_header_symbols_are_exported_listed_and_called():
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_cxx98_consumer_builds_and_links(tmp_path):
-    exe = tmp_path / "consumer"
-    r = subprocess.run(["g++", "-Wall", "-ansi", "-O3", "-pedantic", "-Werror", "-I", str(REPO / "include"),
-                        str(CONSUMER), "-L", str(PKG), "-lttga", f"-Wl,-rpath,{PKG}", "-o", str(exe)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0 and r.stderr == "", r.stderr
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert run.returncode in (0, 2), run.stdout + run.stderr
-    if run.returncode == 2:
-        assert "TT_ERR_DEVICE" in run.stdout and "null-handle checks: 0 wrong" in run.stdout
-    else:
-        assert "null-buffer checks: 0 wrong" in run.stdout
+    build_and_run_consumer(CONSUMER, tmp_path)
 
 
 def test_argument_errors_without_a_device():
@@ -217,14 +200,6 @@ def test_argument_errors_without_a_device():
 
 
 # ---------------------------------------------------------------- the flag, Island, the line
-class Sink:
-    def __init__(self):
-        self.text = ""
-
-    def write(self, s):
-        self.text += s
-
-
 RANGE = "--lahc-walkers must be an integer from 1 to 1024"
 NEEDS = "--lahc-walkers needs --lahc"
 WALK = ["-i", "x.tim", "--lahc", "10"]
@@ -248,23 +223,14 @@ def test_flag_in_the_control_parse():
     assert parse_control([*WALK, "--lahc-walkers", "1024"], out=Sink(), err=Sink())["lahc_walkers"] == 1024
     assert stages.LAHC_WALKERS_NEEDS_LAHC == NEEDS
     for bad, msg in BAD_FLAGS:
-        err = Sink()
-        with pytest.raises(SystemExit) as ex:
-            parse_control(bad, out=Sink(), err=err)
-        assert ex.value.code == 1 and err.text == f"Error: {msg}\n", (bad, err.text)
+        rejected_by_parse_control(bad, msg, exact=True)
 
 
 def test_flag_in_the_native_driver():
-    exe = PKG / "ttga-ga"
-    assert exe.exists(), "ttga-ga not built (make -C timetabling-ga-mpi-openmp_amd)"
     assert f'"{NEEDS}"' in (PKG / "host" / "ttga_ga.cpp").read_text()
     for bad, msg in BAD_FLAGS:
-        r = subprocess.run([str(exe), *bad], capture_output=True, text=True, timeout=60)
-        assert r.returncode == 1 and r.stderr == f"Error: {msg}\n", (bad, r.stderr)
-    # the flag and its value are stripped before the pair count
-    r = subprocess.run([str(exe), "--lahc", "4", "--lahc-walkers", "4", "-s"], capture_output=True, text=True,
-                       timeout=60)
-    assert r.returncode == 1 and "Parse error: Number of command line parameters incorrect" in r.stderr
+        rejected_by_native_driver(bad, msg, exact=True)
+    stripped_before_pair_count(["--lahc", "4", "--lahc-walkers", "4"])
 
 
 def test_flag_is_in_the_table_for_the_tools():

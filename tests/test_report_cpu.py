@@ -10,30 +10,18 @@ import subprocess
 
 import pytest
 
+from stage_checks import Sink, build_and_run_consumer, check_exports, stripped_before_pair_count
 from ttga import native
 from ttga.islands import parse_control
 from ttga.report import report_line
 
 REPO = pathlib.Path(__file__).resolve().parent.parent
-PKG = REPO / "timetabling-ga-mpi-openmp_amd"
 HEADER = REPO / "include" / "ttga_report.h"
 CONSUMER = REPO / "tests" / "boundary_report_cxx98.cpp"
 
 
-def header_symbols():
-    return set(re.findall(r"\b(tt_[a-z_0-9]+)\s*\(", HEADER.read_text()))
-
-
 def test_header_symbols_are_exported_listed_and_called():
-    syms = header_symbols()
-    assert syms == {"tt_eval_parts", "tt_slot_histogram"}
-    assert syms == set(native.REPORT_EXPORTS)
-    assert not syms & set(native.EXPORTS)
-    lib = native.load()
-    for s in syms:
-        assert hasattr(lib, s), s
-    called = set(re.findall(r"\b(tt_[a-z_0-9]+)\s*\(", CONSUMER.read_text()))
-    assert syms <= called, sorted(syms - called)
+    check_exports(HEADER, None, "REPORT_EXPORTS", CONSUMER, {"tt_eval_parts", "tt_slot_histogram"})
     assert native.PART_NAMES == ("room_pairs", "corr_pairs", "unsuitable", "last_slot", "consecutive", "single_class")
     text = HEADER.read_text()
     for k, name in enumerate(native.PART_NAMES):
@@ -57,17 +45,7 @@ def test_load_rejects_a_library_without_the_report_symbols(tmp_path):
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_cxx98_report_consumer_builds_and_links(tmp_path):
-    exe = tmp_path / "consumer"
-    r = subprocess.run(["g++", "-Wall", "-ansi", "-O3", "-pedantic", "-Werror", "-I", str(REPO / "include"),
-                        str(CONSUMER), "-L", str(PKG), "-lttga", f"-Wl,-rpath,{PKG}", "-o", str(exe)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0 and r.stderr == "", r.stderr
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert run.returncode in (0, 2), run.stdout + run.stderr
-    if run.returncode == 2:
-        assert "TT_ERR_DEVICE" in run.stdout and "null-handle checks: 0 wrong" in run.stdout
-    else:
-        assert "null-buffer checks: 0 wrong" in run.stdout
+    build_and_run_consumer(CONSUMER, tmp_path)
 
 
 def test_null_arguments_are_invalid_without_a_device():
@@ -84,18 +62,7 @@ def test_null_arguments_are_invalid_without_a_device():
 
 
 def test_report_flag_is_stripped_before_the_pair_count():
-    exe = PKG / "ttga-ga"
-    assert exe.exists(), "ttga-ga not built (make -C timetabling-ga-mpi-openmp_amd)"
-    r = subprocess.run([str(exe), "--report", "-s"], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 1
-    assert "Parse error: Number of command line parameters incorrect" in r.stderr
-
-    class Sink:
-        def write(self, s):
-            pass
-    with pytest.raises(SystemExit) as ex:
-        parse_control(["--report", "-s"], out=Sink(), err=Sink())
-    assert ex.value.code == 1
+    stripped_before_pair_count(["--report"])
     ctl = parse_control(["-i", "x.tim", "--report", "-s", "42"], out=Sink(), err=Sink())
     assert ctl["report"] is True and ctl["seed"] == 42 and ctl["input"] == "x.tim"
     assert "report" not in parse_control(["-i", "x.tim", "-s", "42"], out=Sink(), err=Sink())

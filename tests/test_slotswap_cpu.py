@@ -6,43 +6,28 @@ the slotSwap line, and the numpy model (tests/slotswap_model.py): its table
 form against its brute-force form and against ttga.validate."""
 import ctypes
 import pathlib
-import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import ttga
 import slotswap_model as sm
+from stage_checks import (Sink, build_and_run_consumer, check_exports, rejected_by_native_driver,
+                          rejected_by_parse_control, stripped_before_pair_count)
 from ttga import native
 from ttga.ga import Island, slot_swap_line
 from ttga.islands import parse_control
 from ttga.validate import evaluate
 
 REPO = pathlib.Path(__file__).resolve().parent.parent
-PKG = REPO / "timetabling-ga-mpi-openmp_amd"
 HEADER = REPO / "include" / "ttga_slotswap.h"
 CONSUMER = REPO / "tests" / "boundary_slotswap_cxx98.cpp"
 UNCAPPED = 2 ** 31 - 1
 
 
-def header_symbols():
-    return set(re.findall(r"\b(tt_[a-z_0-9]+)\s*\(", HEADER.read_text().split("#ifndef TTGA_SLOTSWAP_H")[1]))
-
-
 def test_header_symbols_are_exported_listed_and_called():
-    syms = header_symbols()
-    assert syms == {"tt_slot_swap"}
-    assert syms == set(native.SLOTSWAP_EXPORTS)
-    for other in (native.EXPORTS, native.REPORT_EXPORTS, native.UNIQUE_EXPORTS, native.GREEDY_EXPORTS,
-                  native.KEMPE_EXPORTS):
-        assert not syms & set(other)
-    lib = native.load()
-    for s in syms:
-        assert hasattr(lib, s), s
-    called = set(re.findall(r"\b(tt_[a-z_0-9]+)\s*\(", CONSUMER.read_text()))
-    assert syms <= called, sorted(syms - called)
+    check_exports(HEADER, "TTGA_SLOTSWAP_H", "SLOTSWAP_EXPORTS", CONSUMER, {"tt_slot_swap"})
     assert '#include "ttga.h"' in HEADER.read_text()
     top = (REPO / "include" / "ttga.h").read_text()
     assert "ttga_slotswap.h" in top and "bit 7 (128)" in top
@@ -50,17 +35,7 @@ def test_header_symbols_are_exported_listed_and_called():
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_cxx98_slotswap_consumer_builds_and_links(tmp_path):
-    exe = tmp_path / "consumer"
-    r = subprocess.run(["g++", "-Wall", "-ansi", "-O3", "-pedantic", "-Werror", "-I", str(REPO / "include"),
-                        str(CONSUMER), "-L", str(PKG), "-lttga", f"-Wl,-rpath,{PKG}", "-o", str(exe)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0 and r.stderr == "", r.stderr
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert run.returncode in (0, 2), run.stdout + run.stderr
-    if run.returncode == 2:
-        assert "TT_ERR_DEVICE" in run.stdout and "null-handle checks: 0 wrong" in run.stdout
-    else:
-        assert "null-buffer checks: 0 wrong" in run.stdout
+    build_and_run_consumer(CONSUMER, tmp_path)
 
 
 def test_argument_errors_without_a_device():
@@ -87,14 +62,6 @@ def test_argument_errors_without_a_device():
         assert lib.tt_slot_swap(fake, buf, 0, max_passes, None, None, None, None, None, None) == native.TT_OK
 
 
-class Sink:
-    def __init__(self):
-        self.text = ""
-
-    def write(self, s):
-        self.text += s
-
-
 BAD_FLAGS = (["-i", "x.tim", "--slot-swap", "-1"], ["-i", "x.tim", "--slot-swap"], ["-i", "x.tim", "--slot-swap", "2.5"],
              ["-i", "x.tim", "--slot-swap", "nan"], ["-i", "x.tim", "--slot-swap", "many"])
 
@@ -109,21 +76,13 @@ def test_slot_swap_flag_in_the_control_parse():
                          out=Sink(), err=Sink())
     assert both["slot_swap"] == 64 and both["kempe"] == 0.25 and both["unique"] is True and both["pop"] == 20
     for bad in BAD_FLAGS:
-        err = Sink()
-        with pytest.raises(SystemExit) as ex:
-            parse_control(bad, out=Sink(), err=err)
-        assert ex.value.code == 1 and "--slot-swap must be a non-negative integer" in err.text
+        rejected_by_parse_control(bad, "--slot-swap must be a non-negative integer", exact=True)
 
 
 def test_slot_swap_flag_in_the_native_driver():
-    exe = PKG / "ttga-ga"
-    assert exe.exists(), "ttga-ga not built (make -C timetabling-ga-mpi-openmp_amd)"
     for bad in BAD_FLAGS:
-        r = subprocess.run([str(exe), *bad], capture_output=True, text=True, timeout=60)
-        assert r.returncode == 1 and "--slot-swap must be a non-negative integer" in r.stderr
-    # the flag and its value are stripped before the pair count
-    r = subprocess.run([str(exe), "--slot-swap", "4", "-s"], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 1 and "Parse error: Number of command line parameters incorrect" in r.stderr
+        rejected_by_native_driver(bad, "--slot-swap must be a non-negative integer", exact=True)
+    stripped_before_pair_count(["--slot-swap", "4"])
 
 
 def test_island_rejects_a_negative_slot_swap_before_any_device_call():

@@ -4,53 +4,29 @@ entry points before any device call, the --unique flag's place in the
 Control-style parse, and the format of the unique line both drivers print."""
 import ctypes
 import pathlib
-import re
 import shutil
-import subprocess
 
 import pytest
 
+from stage_checks import Sink, build_and_run_consumer, check_exports, stripped_before_pair_count
 from ttga import native
 from ttga.ga import unique_line
 from ttga.islands import parse_control
 
 REPO = pathlib.Path(__file__).resolve().parent.parent
-PKG = REPO / "timetabling-ga-mpi-openmp_amd"
 HEADER = REPO / "include" / "ttga_unique.h"
 CONSUMER = REPO / "tests" / "boundary_unique_cxx98.cpp"
 
 
-def header_symbols():
-    return set(re.findall(r"\b(tt_[a-z_0-9]+)\s*\(", HEADER.read_text()))
-
-
 def test_header_symbols_are_exported_listed_and_called():
-    syms = header_symbols()
-    assert syms == {"tt_genome_work_bytes", "tt_genome_first", "tt_ga_unique_work_bytes", "tt_ga_replace_unique"}
-    assert syms == set(native.UNIQUE_EXPORTS)
-    assert not syms & set(native.EXPORTS)
-    assert not syms & set(native.REPORT_EXPORTS)
-    lib = native.load()
-    for s in syms:
-        assert hasattr(lib, s), s
-    called = set(re.findall(r"\b(tt_[a-z_0-9]+)\s*\(", CONSUMER.read_text()))
-    assert syms <= called, sorted(syms - called)
+    check_exports(HEADER, None, "UNIQUE_EXPORTS", CONSUMER,
+                  {"tt_genome_work_bytes", "tt_genome_first", "tt_ga_unique_work_bytes", "tt_ga_replace_unique"})
     assert '#include "ttga.h"' in HEADER.read_text()
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_cxx98_unique_consumer_builds_and_links(tmp_path):
-    exe = tmp_path / "consumer"
-    r = subprocess.run(["g++", "-Wall", "-ansi", "-O3", "-pedantic", "-Werror", "-I", str(REPO / "include"),
-                        str(CONSUMER), "-L", str(PKG), "-lttga", f"-Wl,-rpath,{PKG}", "-o", str(exe)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0 and r.stderr == "", r.stderr
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert run.returncode in (0, 2), run.stdout + run.stderr
-    if run.returncode == 2:
-        assert "TT_ERR_DEVICE" in run.stdout and "null-handle checks: 0 wrong" in run.stdout
-    else:
-        assert "null-buffer checks: 0 wrong" in run.stdout
+    build_and_run_consumer(CONSUMER, tmp_path)
 
 
 def _replace_args(handle, N, C, hash_bits, buf, work):
@@ -102,18 +78,7 @@ def test_work_bytes():
 
 
 def test_unique_flag_is_stripped_before_the_pair_count():
-    exe = PKG / "ttga-ga"
-    assert exe.exists(), "ttga-ga not built (make -C timetabling-ga-mpi-openmp_amd)"
-    r = subprocess.run([str(exe), "--unique", "-s"], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 1
-    assert "Parse error: Number of command line parameters incorrect" in r.stderr
-
-    class Sink:
-        def write(self, s):
-            pass
-    with pytest.raises(SystemExit) as ex:
-        parse_control(["--unique", "-s"], out=Sink(), err=Sink())
-    assert ex.value.code == 1
+    stripped_before_pair_count(["--unique"])
     ctl = parse_control(["-i", "x.tim", "--unique", "-s", "42"], out=Sink(), err=Sink())
     assert ctl["unique"] is True and ctl["seed"] == 42 and ctl["input"] == "x.tim"
     assert "unique" not in parse_control(["-i", "x.tim", "-s", "42"], out=Sink(), err=Sink())
