@@ -40,6 +40,32 @@
  * tt_assign_rooms / tt_mutation at R <= 16, keep about 11 to 13 bytes per
  * event and fit up to roughly 12,000 events.
  *
+ * Population size: P * E is not bounded by 32 bits. Row addresses are 64-bit
+ * everywhere, a [P][E] buffer may pass 2^31 and 2^32 bytes, and
+ * tests/test_gpu_large_rows.py runs every entry point there (9,591,083 rows of
+ * 448 events, 2,151,586 of 2,000; tt_eval_parts' event_hcv and tt_lahc_multi's
+ * work buffer past 2^32 bytes too). What bounds P is the launch: most kernels
+ * give every row a workgroup, and HIP runs no launch of more than 2^32 - 1
+ * threads in full (it refuses an exact multiple of 2^32 and otherwise reports
+ * success and runs the count modulo 2^32: a silent wrong result, were it let
+ * through). A call that would need more returns TT_ERR_LIMIT, launches nothing
+ * and leaves every buffer untouched. The largest P (for the GA calls: C for
+ * tt_ga_breed*, N for tt_ga_replace*; tt_lahc_multi: P * walkers):
+ *   16,777,215 (256 threads a row)  tt_eval_parts; tt_eval_variant 2, which
+ *                tt_eval takes above 2,491 events; and with more than 16 rooms
+ *                (the matcher's 4-wave layout) tt_assign_rooms, tt_random_init,
+ *                tt_crossover, tt_ga_breed, tt_greedy_init,
+ *                tt_crossover_guided, tt_ga_breed_guided;
+ *   67,108,863 (one wave a row)     those seven with at most 16 rooms,
+ *                tt_mutation, tt_local_search*, tt_ga_replace,
+ *                tt_ga_replace_unique, tt_kempe_move, tt_slot_swap, tt_lahc,
+ *                tt_lahc_kempe, tt_lahc_kempe_aug, tt_lahc_multi;
+ *   268,435,440  tt_genome_first, with 16 rows to a workgroup of 256;
+ *   536,870,848 or more  tt_eval's tile kernels (7, 8: a workgroup of 256 or
+ *                512 threads per 64 rows, or a grid that does not grow with P).
+ * tt_eval's wide path (13), tt_slot_histogram and tt_lpt_order stay below the
+ * limit for every P an int holds.
+ *
  * Additions with no counterpart in the reference have headers of their own:
  * ttga_report.h, ttga_unique.h, ttga_greedy.h (a greedy constructive
  * initial population, the counterpart of tt_random_init), ttga_kempe.h

@@ -20,7 +20,9 @@ extern "C" {
 
 /* The bytes of tt_lahc_multi's `work` for a population of P rows and `walkers`
  * walkers a row: 8 P + (48 + 2 E) P walkers. 0 for invalid arguments: a NULL
- * problem, P < 0, walkers outside 1 .. 1024, or P * walkers past 2^31 - 1. */
+ * problem, P < 0, walkers outside 1 .. 1024, or P * walkers past 2^31 - 1.
+ * (The formula holds up to there; the call itself takes at most 67,108,863
+ * walkers in all, see below, and refuses a larger product whatever `work` is.) */
 size_t tt_lahc_multi_work_bytes(const tt_problem* p, int P, int walkers);
 
 /* K = `walkers` independent walks of ttga_lahc_kempe_aug.h's tt_lahc_kempe_aug
@@ -72,7 +74,9 @@ size_t tt_lahc_multi_work_bytes(const tt_problem* p, int P, int walkers);
  * set of arguments (the walk that runs is always the one with augmenting
  * rooms, whatever p_kempe and room_rule):
  *     8 * (47 * ceil(E / 64) + 45 + S) + 4 * history + 4 * E + 1,552  <=  65,536,
- * or P * walkers past 2^31 - 1. Either launches nothing and touches no buffer. */
+ * or P * walkers past 67,108,863: every walker is a workgroup of one wave, and
+ * a launch holds at most 2^32 - 1 threads (ttga.h, "Population size"). Either
+ * launches nothing and touches no buffer. */
 int tt_lahc_multi(const tt_problem* p, uint8_t* slot, uint8_t* room, int64_t* rng, int P, int walkers, int steps,
                   int history, double p_swap, double p_kempe, int max_chain, int room_rule, int32_t* scv,
                   int32_t* penalty, int32_t* gain, int32_t* accepted, int32_t* best_step, int32_t* kempe_stats,

@@ -260,12 +260,12 @@ static uint32_t cx_host_pm_pow(long n) {
 }
 
 // the rooms come from the matcher: its limit is checked before anything is launched
-static int cx_check_limit(const tt_problem* p) {
+static int cx_check_limit(const char* fn, const tt_problem* p, int rows) {
     if (match_scratch_bytes(p->E, p->R, match_wide(p->R) ? kWideWaves : 1) > 160 * 1024) {
         set_error("instance too large for the matcher");
         return TT_ERR_LIMIT;
     }
-    return TT_OK;
+    return check_rows_grid(fn, p, rows, true);
 }
 
 static int cx_launch(const tt_problem* p, const CxArgs& a, hipStream_t st) {
@@ -291,7 +291,7 @@ extern "C" int tt_crossover_guided(const tt_problem* p, const uint8_t* slot1, co
     if (P == 0) return TT_OK;
     if (!slot1 || !slot2 || !slot || !room) { set_error("tt_crossover_guided: null population buffer"); return TT_ERR_INVALID; }
     if (!order || !rng) { set_error("tt_crossover_guided: null order or rng buffer"); return TT_ERR_INVALID; }
-    int rc = cx_check_limit(p);
+    int rc = cx_check_limit("tt_crossover_guided", p, P);
     if (rc) return rc;
     if ((rc = use_device(p))) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -313,7 +313,7 @@ extern "C" int tt_ga_breed_guided(const tt_problem* p, const uint8_t* pop_slot, 
     }
     if (C == 0) return TT_OK;
     if (!order) { set_error("tt_ga_breed_guided: null order buffer"); return TT_ERR_INVALID; }
-    if ((rc = cx_check_limit(p))) return rc;
+    if ((rc = cx_check_limit("tt_ga_breed_guided", p, C))) return rc;
     if ((rc = use_device(p))) return rc;
     hipStream_t st = (hipStream_t)stream;
     CxArgs a{pop_slot, pop_room, pop_penalty, N, p_cross, p_mut, skip_init_draws, cx_host_pm_pow(3L * p->E - 1), order,

@@ -1395,6 +1395,7 @@ extern "C" int tt_eval_variant(const tt_problem* p, const uint8_t* slot, const u
             // ablate 64 forces the persistent grid, 128 the one-tile grid (comparisons).
             const bool persist = (ablate & 64) || (two && !(ablate & 128));
             const int grid = persist ? std::min(tiles, std::max(1, per_cu) * p->num_cus) : tiles;
+            if (const int lim = check_grid("tt_eval", grid, 64 * NW)) return lim;
             hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), bytes, st, p->dev, slot, room, P, hcv, scv,
                                feasible, penalty, ablate);
             return TT_OK;
@@ -1427,6 +1428,7 @@ extern "C" int tt_eval_variant(const tt_problem* p, const uint8_t* slot, const u
     } else {
         const size_t lds = block_lds_bytes(E, R);
         if (lds > 160 * 1024) { set_error("instance too large for the block kernel"); return TT_ERR_LIMIT; }
+        if ((rc = check_grid("tt_eval", P, kBlockThreads))) return rc;
         hipLaunchKernelGGL(eval_block_kernel, dim3(P), dim3(kBlockThreads), lds, st, p->dev, slot, room, P, hcv,
                            scv, feasible, penalty);
     }

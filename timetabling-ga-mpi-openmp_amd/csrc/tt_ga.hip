@@ -459,6 +459,7 @@ extern "C" int tt_ga_breed(const tt_problem* p, const uint8_t* pop_slot, const u
         return TT_ERR_INVALID;
     }
     if (C == 0) return TT_OK;
+    if ((rc = check_rows_grid("tt_ga_breed", p, C, true))) return rc;
     if ((rc = use_device(p))) return rc;
     hipStream_t st = (hipStream_t)stream;
     const uint32_t jump_skip = host_pm_pow(3L * p->E - 1), jump_e = host_pm_pow(p->E);
@@ -519,8 +520,9 @@ extern "C" int tt_ga_replace(const tt_problem* p, uint8_t* pop_slot, uint8_t* po
         set_error("tt_ga_replace: bad arguments");
         return TT_ERR_INVALID;
     }
-    int rc = use_device(p);
+    int rc = check_rows_grid("tt_ga_replace", p, N, false);
     if (rc) return rc;
+    if ((rc = use_device(p))) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int E = p->E, NP = pow2_at_least(N);
     const GaWork gw = ga_work_layout(work, N, E);

@@ -191,6 +191,7 @@ extern "C" int tt_greedy_init(const tt_problem* p, const int32_t* order, int64_t
         set_error("instance too large for the matcher");
         return TT_ERR_LIMIT;
     }
+    if ((rc = check_rows_grid("tt_greedy_init", p, P, true))) return rc;
     if ((rc = use_device(p))) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (p->dev.EW64 <= kGreedyRegWords) {

@@ -75,6 +75,31 @@ inline int lds_resident_limit(size_t lds_bytes) {
     return blocks == 0 ? 1 << 30 : (int)(128 / blocks);
 }
 
+// HIP runs no launch whose gridDim.x * blockDim.x passes 2^32 - 1 in full: an
+// exact multiple of 2^32 is refused (hipErrorInvalidConfiguration), anything
+// else is accepted with hipSuccess and runs the product modulo 2^32 threads
+// (2^24 + 3 workgroups of 256: three of them), a silent wrong result. An entry
+// point whose grid grows with the population therefore asks before its first launch:
+// TT_OK, or TT_ERR_LIMIT with nothing launched and every buffer untouched
+// (include/ttga.h, "Population size").
+constexpr long long kMaxGridThreads = 0xFFFFFFFFll;
+inline int check_grid(const char* fn, long long blocks, int threads) {
+    if (blocks * threads <= kMaxGridThreads) return TT_OK;
+    set_error(std::string(fn) + ": population too large for one launch (" + std::to_string(blocks) +
+              " workgroups of " + std::to_string(threads) + " threads; at most " +
+              std::to_string(kMaxGridThreads / threads) + ")");
+    return TT_ERR_LIMIT;
+}
+
+// check_grid for a call that gives every one of `rows` rows a workgroup of one
+// wave, and with `rooms` also one of assign_rooms_kernel's, which has
+// kAssignWideThreads threads in the matcher's wide layout (R > 16, tt_match.h;
+// tt_rooms.hip asserts both).
+constexpr int kAssignWideThreads = 256;
+inline int check_rows_grid(const char* fn, const tt_problem* p, long long rows, bool rooms) {
+    return check_grid(fn, rows, rooms && p->R > 16 ? kAssignWideThreads : 64);
+}
+
 // Common argument checks for population entry points.
 int check_pop_args(const tt_problem* p, int P, const void* a, const void* b);
 

@@ -166,6 +166,7 @@ extern "C" int tt_kempe_move(const tt_problem* p, uint8_t* slot, uint8_t* room, 
         set_error("instance too large for the Kempe move");
         return TT_ERR_LIMIT;
     }
+    if ((rc = check_rows_grid("tt_kempe_move", p, P, false))) return rc;
     if ((rc = use_device(p))) return rc;
     hipLaunchKernelGGL(kempe_kernel, dim3(P), dim3(64), lds, (hipStream_t)stream, p->dev, slot, room, rng, P, prob,
                        max_chain, chain_len, (unsigned)match_scratch_bytes(p->E, p->R));

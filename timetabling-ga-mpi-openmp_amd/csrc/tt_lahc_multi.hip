@@ -133,6 +133,7 @@ extern "C" int tt_lahc_multi(const tt_problem* p, uint8_t* slot, uint8_t* room, 
         set_error("tt_lahc_multi: P * walkers above 2^31 - 1");
         return TT_ERR_LIMIT;
     }
+    if ((rc = check_grid(fn, (long long)P * walkers, 64))) return rc;     // one wave per walker
     if (walkers == 1) {
         int32_t* g = gain ? gain : walker_gain;
         if ((rc = tt_lahc_kempe_aug(p, slot, room, rng, P, steps, history, p_swap, p_kempe, max_chain, room_rule, scv,

@@ -1012,7 +1012,8 @@ inline int lahc_check_args(const char* fn, LahcKind kind, const tt_problem* p, i
     int rc = lahc_check_rows(fn, p, P, slot, room, rng);
     if (!rc) rc = lahc_check_walk(fn, kind, steps, history, p_swap, p_kempe, max_chain, room_rule);
     if (rc || P == 0) return rc;
-    return lahc_check_lds(kind, p, history, lds);
+    if ((rc = lahc_check_lds(kind, p, history, lds))) return rc;
+    return check_rows_grid(fn, p, P, false);
 }
 
 }  // namespace ttga

@@ -1841,6 +1841,7 @@ extern "C" int tt_local_search_eval(const tt_problem* p, uint8_t* slot, uint8_t*
     if (nout != 0 && nout != 4) { set_error("evaluation outputs: all four or none"); return TT_ERR_INVALID; }
     const LsEvalOut eout{hcv, scv, feasible, penalty};
     if (max_steps < 0) { set_error("negative max_steps"); return TT_ERR_INVALID; }
+    if ((rc = check_rows_grid("tt_local_search", p, P, false))) return rc;
     if ((rc = use_device(p))) return rc;
     const int smf = ls_mask_students(p, kMaxSlotEvents, local_search_kernel<kMaxSlotEvents>, P);
     const LsLayout Lf = ls_layout(p->E, p->R, p->dev.EW64, kMaxSlotEvents, smf);

@@ -272,6 +272,7 @@ extern "C" int tt_eval_parts(const tt_problem* p, const uint8_t* slot, const uin
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int E = p->E, R = p->R, W = p->dev.EW64;
+    if ((rc = check_grid("tt_eval_parts", P, kPartsThreads))) return rc;
     if (W <= 7) {
         const size_t lds = bits_lds_bytes(E, R, W);
 #define TT_BITS(WC)                                                                                              \

@@ -174,6 +174,9 @@ __global__ __launch_bounds__(64) void mutation_kernel(DevProblem pb, uint8_t* __
 
 static int tile_stride(int E) { return (E + 3) & ~3; }
 
+// (and match_wide is R > 16, as there)
+static_assert(64 * kWideWaves == kAssignWideThreads, "check_rows_grid (tt_internal.h) states assign_rooms_kernel's workgroup");
+
 int launch_assign_masked(const tt_problem* p, const uint8_t* slot, uint8_t* room, int P, const uint8_t* mask,
                          uint8_t bit, hipStream_t st) {
     const int nw = match_wide(p->R) ? kWideWaves : 1;
@@ -203,6 +206,7 @@ using namespace ttga;
 extern "C" int tt_assign_rooms(const tt_problem* p, const uint8_t* slot, uint8_t* room, int P, void* stream) {
     int rc = check_pop_args(p, P, slot, room);
     if (rc || P == 0) return rc;
+    if ((rc = check_rows_grid("tt_assign_rooms", p, P, true))) return rc;
     if ((rc = use_device(p))) return rc;
     return launch_assign(p, slot, room, P, (hipStream_t)stream);
 }
@@ -211,6 +215,7 @@ extern "C" int tt_random_init(const tt_problem* p, int64_t* rng, uint8_t* slot, 
     int rc = check_pop_args(p, P, slot, room);
     if (rc || P == 0) return rc;
     if (!rng) { set_error("null rng buffer"); return TT_ERR_INVALID; }
+    if ((rc = check_rows_grid("tt_random_init", p, P, true))) return rc;
     if ((rc = use_device(p))) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int SP = tile_stride(p->E);
@@ -225,6 +230,7 @@ extern "C" int tt_crossover(const tt_problem* p, const uint8_t* slot1, const uin
     int rc = check_pop_args(p, P, slot1, slot2);
     if (rc || P == 0) return rc;
     if (!rng || !slot || !room) { set_error("null buffer"); return TT_ERR_INVALID; }
+    if ((rc = check_rows_grid("tt_crossover", p, P, true))) return rc;
     if ((rc = use_device(p))) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int SP = tile_stride(p->E);
@@ -239,6 +245,7 @@ extern "C" int tt_mutation(const tt_problem* p, uint8_t* slot, uint8_t* room, in
     int rc = check_pop_args(p, P, slot, room);
     if (rc || P == 0) return rc;
     if (!rng) { set_error("null rng buffer"); return TT_ERR_INVALID; }
+    if ((rc = check_rows_grid("tt_mutation", p, P, false))) return rc;
     if ((rc = use_device(p))) return rc;
     return launch_mutation_masked(p, slot, room, rng, P, nullptr, 0, (hipStream_t)stream);
 }

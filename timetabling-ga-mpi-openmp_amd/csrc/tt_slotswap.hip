@@ -286,6 +286,7 @@ extern "C" int tt_slot_swap(const tt_problem* p, uint8_t* slot, int P, int max_p
         set_error("instance too large for the timeslot swap");
         return TT_ERR_LIMIT;
     }
+    if ((rc = check_rows_grid("tt_slot_swap", p, P, false))) return rc;
     if ((rc = use_device(p))) return rc;
     hipLaunchKernelGGL(slot_swap_kernel, dim3(P), dim3(64), lds, (hipStream_t)stream, p->dev, slot, P, max_passes, scv,
                        penalty, gain, passes, perm);

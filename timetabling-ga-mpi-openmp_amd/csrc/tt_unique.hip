@@ -88,8 +88,9 @@ __global__ __launch_bounds__(256) void hash_rows_kernel(int E, const uint8_t* __
                                                         const uint8_t* __restrict__ r1, int n1, uint32_t mask,
                                                         uint32_t* __restrict__ hash0, uint64_t* __restrict__ keys1,
                                                         int NP1, uint8_t* __restrict__ keep) {
-    const int gt = blockIdx.x * 256 + threadIdx.x;
-    for (int i = n1 + gt; i < NP1; i += gridDim.x * 256) keys1[i] = ~0ull;
+    // (long: the grid has kHashLanes threads a row, so n1 + gt passes 2^31 from 1.3 * 10^8 rows on)
+    const long gt = (long)blockIdx.x * 256 + threadIdx.x;
+    for (long i = n1 + gt; i < NP1; i += (long)gridDim.x * 256) keys1[i] = ~0ull;
     const int sub = threadIdx.x & (kHashLanes - 1);
     const long row = (long)blockIdx.x * kHashRows + (threadIdx.x / kHashLanes);
     if (row >= (long)n0 + n1) return;                          // uniform over the row's lanes
@@ -354,6 +355,7 @@ extern "C" int tt_genome_first(const tt_problem* p, const uint8_t* slot, const u
     if (P > 0 && (!first || !work)) { set_error("null output or work buffer"); return TT_ERR_INVALID; }
     if (!hash_bits_ok(hash_bits)) { set_error("hash_bits must be 0..31"); return TT_ERR_INVALID; }
     if (P == 0) return TT_OK;
+    if ((rc = check_grid("tt_genome_first", ((long long)P + kHashRows - 1) / kHashRows, 256))) return rc;
     if ((rc = use_device(p))) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int E = p->E, PP = padded(P);
@@ -396,8 +398,9 @@ extern "C" int tt_ga_replace_unique(const tt_problem* p, uint8_t* pop_slot, uint
         if (n_kept) TT_HIP(hipMemsetAsync(n_kept, 0, sizeof(int32_t), st));
         return TT_OK;
     }
-    int rc = use_device(p);
+    int rc = check_rows_grid("tt_ga_replace_unique", p, N, false);
     if (rc) return rc;
+    if ((rc = use_device(p))) return rc;
     const int E = p->E, NP = pow2_at_least(N), CP = padded(C);
     const GaWork gw = ga_work_layout(work, N, E);
     const UniqueWork uw = unique_work_layout(work, N, C, E);
