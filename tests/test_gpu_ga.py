@@ -47,12 +47,19 @@ def test_breed_vs_oracle(sm, N, C, skip):
 # C > 8,192; for C <= 8,192 the merge of the survivors with the sorted children
 # when the survivors are in order (presorted: as a previous tt_ga_replace leaves
 # them; "migrant": one survivor out of order, as after a migration), else the
-# one-workgroup fallback sort
+# one-workgroup fallback sort. The last six sit on the path boundaries: child keys
+# padded to 256 (the register sort) and to 512 (the smallest tiles + ranks sort), the
+# last C of the merge form and the first of the full sort, and the fallback behind
+# either child sort (three survivors, the middle one out of order) over 512 and
+# 16,384 keys
 @pytest.mark.parametrize("N,C,order", [(10, 1, "random"), (10, 4, "random"), (300, 300, "random"),
                                        (5000, 100, "random"), (20000, 3000, "random"), (65536, 8192, "random"),
                                        (20000, 9000, "random"), (10, 4, "presorted"), (300, 300, "presorted"),
                                        (5000, 100, "presorted"), (65536, 8192, "presorted"),
-                                       (65536, 8192, "migrant"), (4096, 1, "migrant")])
+                                       (65536, 8192, "migrant"), (4096, 1, "migrant"),
+                                       (256, 256, "presorted"), (257, 257, "presorted"), (259, 256, "migrant"),
+                                       (8192, 8192, "presorted"), (8193, 8193, "presorted"),
+                                       (8195, 8192, "migrant")])
 def test_replace_vs_oracle(sm, N, C, order):
     inst, dp, o = sm
     rng = np.random.default_rng(N + C)
@@ -69,10 +76,15 @@ def test_replace_vs_oracle(sm, N, C, order):
         if order == "migrant":
             pop["penalty"][(N - C) // 2] = 39 + 1              # one survivor out of order
     exp = o.ga_replace(pop, ch)
+    # merged positions: survivors 0..N-C-1, then child c at N-C+c; the new pop[0] is the first in key order
+    merged = np.concatenate([pop["penalty"][:N - C], ch["penalty"]]).astype(np.uint32)
+    src = int(np.lexsort((np.arange(N), merged))[0])
     gpop = {k: dev(v) for k, v in pop.items()}
-    dp.ga_replace(gpop, {k: dev(v) for k, v in ch.items()}, dp.ga_work(N))
+    work = dp.ga_work(N)
+    dp.ga_replace(gpop, {k: dev(v) for k, v in ch.items()}, work)
     for k in KEYS:
         assert np.array_equal(host(gpop[k]), exp[k]), k
+    assert dp.ga_work_source(work, N) == src
 
 
 @pytest.mark.parametrize("N,C,gens,lpt", [(10, 1, 12, None), (16, 8, 6, None), (64, 48, 4, True)])

@@ -228,7 +228,8 @@ def build_case(rng, inst, N, C, case):
 
 
 @pytest.mark.parametrize("case", CASES)
-@pytest.mark.parametrize("N,C", [(10, 1), (64, 16), (300, 300), (4096, 2048), (9000, 8500)])
+@pytest.mark.parametrize("N,C", [(10, 1), (64, 16), (300, 300), (4096, 2048), (9000, 8500), (257, 257),
+                                 (8192, 8192)])
 def test_replace_unique_vs_oracle(e20, N, C, case):
     inst, dp, o = e20
     rng = np.random.default_rng(N * 7 + C + CASES.index(case))

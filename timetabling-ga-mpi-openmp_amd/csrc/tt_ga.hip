@@ -9,7 +9,10 @@
 //                    next() < p_mut   ? randomMove                           (ga.cpp:569-571)
 //   tt_ga_replace  children overwrite positions N-C..N-1 (ga.cpp:582 with
 //                  C = 1), then the population is sorted by penalty
-//                  ascending (ga.cpp:583); ties keep position order.
+//                  ascending (ga.cpp:583); ties keep position order. Its
+//                  sorts, merge form, row movers and work carve also serve
+//                  tt_ga_replace_unique (tt_unique.hip), through
+//                  tt_replace_internal.h: every step's kernel is here, once.
 #include <algorithm>
 
 #include "tt_internal.h"
@@ -96,7 +99,9 @@ static uint32_t host_pm_pow(long n) {
 
 // ---------------------------------------------------------------- replace + sort
 // keys are sort_key(penalty, position) (tt_replace_internal.h): penalties compare as unsigned
-// keys of the merged population: positions < N-C from pop, the rest from the children
+// keys of the merged population: positions < N-C from pop, the rest from the children.
+// The one step tt_ga_replace_unique does not share: its full sort reads kept keys that
+// keep_scan left (unique_keys_kernel); there is no child-key array of C > kSortTile keys here
 __global__ void replace_keys_kernel(const int32_t* __restrict__ pen, const int32_t* __restrict__ cpen, int N, int C,
                                     int NP, uint64_t* __restrict__ keys) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -106,28 +111,28 @@ __global__ void replace_keys_kernel(const int32_t* __restrict__ pen, const int32
     keys[i] = sort_key(i < k ? pen[i] : cpen[i - k], i);
 }
 
-// bitonic sort of NP (power of two) u64 keys: one workgroup in LDS when NP <= 4096 ...
-__global__ __launch_bounds__(1024) void bitonic_lds_kernel(uint64_t* __restrict__ keys, int NP) {
-    __shared__ uint64_t sk[4096];
-    for (int i = threadIdx.x; i < NP; i += blockDim.x) sk[i] = keys[i];
+// bitonic sort of NP (power of two) u64 keys. Fewer than 8 keys (NP = 1, 2 or 4, below
+// sort_reg_kernel<8>'s smallest tile): NP threads of one wave in LDS ...
+__global__ __launch_bounds__(64) void bitonic_lds_kernel(uint64_t* __restrict__ keys, int NP) {
+    __shared__ uint64_t sk[4];
+    const int i = threadIdx.x;
+    sk[i] = keys[i];
     __syncthreads();
     for (int k = 2; k <= NP; k <<= 1) {
         for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < NP; i += blockDim.x) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const uint64_t x = sk[i], y = sk[l];
-                    const bool up = (i & k) == 0;
-                    if ((x > y) == up) { sk[i] = y; sk[l] = x; }
-                }
+            const int l = i ^ j;
+            if (l > i) {
+                const uint64_t x = sk[i], y = sk[l];
+                const bool up = (i & k) == 0;
+                if ((x > y) == up) { sk[i] = y; sk[l] = x; }
             }
             __syncthreads();
         }
     }
-    for (int i = threadIdx.x; i < NP; i += blockDim.x) keys[i] = sk[i];
+    keys[i] = sk[i];
 }
 
-// ... above that, tiles of kSortTile keys in LDS: bitonic_tile_kernel runs, per
+// ... above kSortTile keys, tiles of kSortTile keys in LDS: bitonic_tile_kernel runs, per
 // tile, the stages k <= kSortTile completely (full) or, for a stage k above the
 // tile, its steps j < kSortTile (after the global steps j >= kSortTile). The
 // direction of a pair is (i & k) of its global index i, as in one global pass.
@@ -166,57 +171,62 @@ __global__ void bitonic_step_kernel(uint64_t* __restrict__ keys, int NP, int k, 
     }
 }
 
-// ---- merge form of the sort: the survivors (positions < k = N-C)
-// of a population that a previous tt_ga_replace left sorted are already in key
-// order, so the sorted merged population is the merge of them with the C
-// children's keys sorted on their own (one workgroup in LDS for C <= kSortTile).
-// Keys are unique (positions), so the merge equals the full sort. The survivors'
-// order is checked on the device; when it does not hold (a migrant written into
-// pop[N-2] survives when C = 1) a one-workgroup full sort runs instead. C = 0
-// (the initial sort) takes the tiled sort directly.
+// ---- merge form of the sort, of tt_ga_replace (D = C children, host value) and of
+// tt_ga_replace_unique (D = the kept children, a device word): the survivors
+// (positions < k = N-D) of a population that a previous replacement left sorted
+// are already in key order, so the sorted merged population is the merge of them
+// with the D children's keys sorted on their own (one or two launches for
+// C <= kSortTile). Keys are unique (positions), so the merge equals the full sort.
+// The survivors' order is checked on the device; when it does not hold (a migrant
+// written into pop[N-2] survives when C = 1) a one-workgroup full sort runs
+// instead. C = 0 (the initial sort) takes the tiled sort directly.
 
 // kPrepBlocks workgroups: flag[g] = 1 when workgroup g's share of the survivors
-// is in key order (all of them together: the survivors are); ckeys = the
-// children's keys (padded to CP), sorted by the next launch
-__global__ __launch_bounds__(256) void replace_prep_kernel(const int32_t* __restrict__ pen,
-                                                           const int32_t* __restrict__ cpen, int N, int C, int CP,
+// is in key order (all of them together: the survivors are). With cpen (tt_ga_replace,
+// whose child keys come from penalties; tt_ga_replace_unique's from keep_scan) also
+// ckeys = the children's keys base + c (padded to CP), sorted by the next launch
+__global__ __launch_bounds__(256) void replace_prep_kernel(const int32_t* __restrict__ pen, int N, ChildCount count,
+                                                           const int32_t* __restrict__ cpen, int base, int CP,
                                                            uint64_t* __restrict__ ckeys, int32_t* __restrict__ flag) {
-    const int k = N - C;
+    const int D = child_count(count), k = N - D;
     const int gt = blockIdx.x * blockDim.x + threadIdx.x, nth = gridDim.x * blockDim.x;
-    for (int i = gt; i < CP; i += nth) ckeys[i] = i < C ? sort_key(cpen[i], k + i) : ~0ull;
+    if (cpen)
+        for (int i = gt; i < CP; i += nth) ckeys[i] = i < D ? sort_key(cpen[i], base + i) : ~0ull;
     bool ok = true;
     for (int i = gt; i + 1 < k; i += nth) ok &= (uint32_t)pen[i] <= (uint32_t)pen[i + 1];
     ok = __syncthreads_and(ok);
     if (threadIdx.x == 0) flag[blockIdx.x] = ok ? 1 : 0;
 }
 
-// merge path: output i takes the i-th smallest of survivors (pen[a], a) and ckeys
-__global__ void replace_merge_kernel(const int32_t* __restrict__ pen, int N, int C, const uint64_t* __restrict__ ckeys,
-                                     const int32_t* __restrict__ flag, uint64_t* __restrict__ mkeys) {
+// merge path: output i takes the i-th smallest of survivors (pen[a], a) and the D sorted ckeys
+__global__ void replace_merge_kernel(const int32_t* __restrict__ pen, int N, ChildCount count,
+                                     const uint64_t* __restrict__ ckeys, const int32_t* __restrict__ flag,
+                                     uint64_t* __restrict__ mkeys) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (!survivors_sorted(flag) || i >= N) return;
-    const int k = N - C;
-    int lo = max(0, i - C), hi = min(i, k);
+    const int D = child_count(count), k = N - D;
+    int lo = max(0, i - D), hi = min(i, k);
     while (lo < hi) {
         const int mid = (lo + hi) >> 1;
         if (sort_key(pen[mid], mid) < ckeys[i - 1 - mid]) lo = mid + 1;
         else hi = mid;
     }
     const int a = lo, b = i - a;
-    const uint64_t ka = a < k ? sort_key(pen[a], a) : ~0ull, kb = b < C ? ckeys[b] : ~0ull;
+    const uint64_t ka = a < k ? sort_key(pen[a], a) : ~0ull, kb = b < D ? ckeys[b] : ~0ull;
     mkeys[i] = ka < kb ? ka : kb;
 }
 
-// the fallback: full bitonic sort of keys[0..NP) by one workgroup in global memory
-// (keys, 8 B each, stay L2-resident); nothing to do when the merge ran
+// the fallback (a survivor out of order): the survivors' keys and, behind them, the
+// D child keys, sorted by one workgroup in global memory (keys, 8 B each, stay
+// L2-resident); nothing to do when the merge ran
 __global__ __launch_bounds__(1024) void replace_fallback_sort_kernel(const int32_t* __restrict__ pen,
-                                                                     const int32_t* __restrict__ cpen, int C,
-                                                                     uint64_t* __restrict__ keys, int NP,
-                                                                     const int32_t* __restrict__ flag,
+                                                                     const uint64_t* __restrict__ ckeys,
+                                                                     ChildCount count, uint64_t* __restrict__ keys,
+                                                                     int NP, const int32_t* __restrict__ flag,
                                                                      uint64_t* __restrict__ mkeys, int N) {
     if (survivors_sorted(flag)) return;
-    for (int i = threadIdx.x; i < NP; i += blockDim.x)          // the keys (replace_keys_kernel's)
-        keys[i] = i >= N ? ~0ull : sort_key(i < N - C ? pen[i] : cpen[i - (N - C)], i);
+    const int k = N - child_count(count);
+    for (int i = threadIdx.x; i < NP; i += blockDim.x) keys[i] = merged_key(pen, ckeys, N, k, i);
     __threadfence_block();
     __syncthreads();
     bitonic_global(keys, NP);
@@ -337,8 +347,9 @@ __global__ __launch_bounds__(256) void rank_scatter_kernel(const uint64_t* __res
     if (b == 0) out[r] = x;
 }
 
-// gather the sorted population into the work rows (one wave per row)
-__global__ __launch_bounds__(64) void replace_gather_kernel(int E, int N, int C, const uint64_t* __restrict__ keys,
+// gather the sorted population into the work rows (one wave per row); a key's low
+// word is a survivor's position (< base) or base + the child's index
+__global__ __launch_bounds__(64) void replace_gather_kernel(int E, int base, const uint64_t* __restrict__ keys,
                                                             const uint8_t* __restrict__ ps, const uint8_t* __restrict__ pr,
                                                             const int32_t* __restrict__ ph, const int32_t* __restrict__ psc,
                                                             const uint8_t* __restrict__ pf, const int32_t* __restrict__ pp,
@@ -350,9 +361,8 @@ __global__ __launch_bounds__(64) void replace_gather_kernel(int E, int N, int C,
     const int i = blockIdx.x;
     const int src = (int)(keys[i] & 0xFFFFFFFFu);
     if (i == 0 && threadIdx.x == 0) *best_src = src;          // the new pop[0]'s merged position
-    const int k = N - C;
-    const bool child = src >= k;
-    const int r = child ? src - k : src;
+    const bool child = src >= base;
+    const int r = child ? src - base : src;
     const uint8_t* s = (child ? cs : ps) + (long)r * E;
     const uint8_t* m = (child ? cr : pr) + (long)r * E;
     copy_rows2(ws + (long)i * E, s, wr + (long)i * E, m, E, threadIdx.x);
@@ -407,14 +417,16 @@ __global__ __launch_bounds__(256) void lpt_rank_order_kernel(const uint64_t* __r
     if (b == 0 && r < n) order[r] = (int32_t)(uint32_t)x;
 }
 
-// ascending bitonic sort of NP (a power of two) u64 keys on stream st
+// ascending bitonic sort of NP (a power of two) u64 keys on stream st: fewer than 8
+// keys by bitonic_lds_kernel, 8..kSortTile in the registers of one workgroup
+// (sort_reg_kernel<8>), more in tiles of kSortTile
 void sort_keys(uint64_t* keys, int NP, hipStream_t st) {
-    if (NP >= 8 && NP <= kSortTile) {
-        hipLaunchKernelGGL(sort_reg_kernel<8>, dim3(1), dim3(std::max(64, NP / 8)), 0, st, keys, NP);
+    if (NP < 8) {
+        hipLaunchKernelGGL(bitonic_lds_kernel, dim3(1), dim3(NP), 0, st, keys, NP);
         return;
     }
-    if (NP <= 4096) {
-        hipLaunchKernelGGL(bitonic_lds_kernel, dim3(1), dim3(std::min(NP, 1024)), 0, st, keys, NP);
+    if (NP <= kSortTile) {
+        hipLaunchKernelGGL(sort_reg_kernel<8>, dim3(1), dim3(std::max(64, NP / 8)), 0, st, keys, NP);
         return;
     }
     // NP / kSortTile tiles: 1 + sum over the stages above the tile of (global steps + 1)
@@ -429,14 +441,34 @@ void sort_keys(uint64_t* keys, int NP, hipStream_t st) {
 }
 
 // NP keys in [2*kRankTile, kSortTile]: sorted by tiles + ranks
-bool use_rank_sort(int NP) { return NP >= 2 * kRankTile && NP <= kSortTile; }
+static bool use_rank_sort(int NP) { return NP >= 2 * kRankTile && NP <= kSortTile; }
 // the tiles of the rank sort (ranks are then counted by the caller's kernel)
-void sort_rank_tiles(uint64_t* keys, int NP, hipStream_t st) {
+static void sort_rank_tiles(uint64_t* keys, int NP, hipStream_t st) {
     hipLaunchKernelGGL(sort_reg_kernel<4>, dim3(NP / kRankTile), dim3(kRankTile / 4), 0, st, keys, kRankTile);
 }
-void rank_scatter(const uint64_t* keys, int NP, uint64_t* out, hipStream_t st) {
-    const int NT = NP / kRankTile;
-    hipLaunchKernelGGL(rank_scatter_kernel, dim3(NP * NT / 256), dim3(256), 0, st, keys, NP, NT, out);
+
+const uint64_t* sort_any(uint64_t* keys, uint64_t* other, int NP, hipStream_t st) {
+    if (use_rank_sort(NP)) {
+        const int NT = NP / kRankTile;
+        sort_rank_tiles(keys, NP, st);
+        hipLaunchKernelGGL(rank_scatter_kernel, dim3(NP * NT / 256), dim3(256), 0, st, keys, NP, NT,
+                           other);
+        return other;
+    }
+    sort_keys(keys, NP, st);
+    return keys;
+}
+
+const uint64_t* merge_sorted_keys(const int32_t* pen, int N, ChildCount count, const int32_t* cpen, int base, int CP,
+                                  const ChildWork& cw, const GaWork& w, hipStream_t st) {
+    hipLaunchKernelGGL(replace_prep_kernel, dim3(kPrepBlocks), dim3(256), 0, st, pen, N, count, cpen, base, CP, cw.keys,
+                       cw.flag);
+    const uint64_t* csorted = sort_any(cw.keys, cw.sorted, CP, st);
+    hipLaunchKernelGGL(replace_merge_kernel, dim3((N + 255) / 256), dim3(256), 0, st, pen, N, count, csorted,
+                       cw.flag, w.mkeys);
+    hipLaunchKernelGGL(replace_fallback_sort_kernel, dim3(1), dim3(1024), 0, st, pen, csorted, count, w.keys,
+                       pow2_at_least(N), cw.flag, w.mkeys, N);
+    return w.mkeys;
 }
 
 // launched from tt_rooms.hip (masked variants of the matcher and of mutation)
@@ -470,43 +502,45 @@ extern "C" int tt_ga_breed(const tt_problem* p, const uint8_t* pop_slot, const u
     return launch_mutation_masked(p, child_slot, child_room, rng, C, child_flags, kFlagMutate, st);
 }
 
-// work layout: sort keys [pow2(N)] u64 | slot rows [N][E] | room rows [N][E] |
-// meta [N][4] i32 | the source slot (256 B, written only by tt_ga_replace) |
-// merged keys [N] u64 | child keys [kSortTile] u64 | merge flag (256 B) |
-// sorted child keys [kSortTile] u64
-static size_t work_source_offset(int N, int E) {
-    const size_t NP = (size_t)pow2_at_least(N);
-    return align256(8 * NP) + 2 * align256((size_t)N * E) + align256(16 * (size_t)N);
-}
-static size_t work_merge_offset(int N, int E) { return work_source_offset(N, E) + 256; }
-
 namespace ttga {
+// work layout: sort keys [pow2(N)] u64 | slot rows [N][E] | room rows [N][E] |
+// meta [N][4] i32 | the source word (256 B) | merged keys [N] u64 |
+// child keys [kSortTile] u64 | survivors-in-order flags (256 B) | sorted child
+// keys [kSortTile] u64 (the last three: tt_ga_replace's merge form only)
 GaWork ga_work_layout(void* work, int N, int E) {
-    uint8_t* w = (uint8_t*)work;
+    Carve c{(uint8_t*)work};
     GaWork g;
-    g.keys = (uint64_t*)w;
-    g.ws = w + align256(8 * (size_t)pow2_at_least(N));
-    g.wr = g.ws + align256((size_t)N * E);
-    g.wm = (int32_t*)(g.wr + align256((size_t)N * E));
-    g.source = (int32_t*)(w + work_source_offset(N, E));
-    g.mkeys = (uint64_t*)(w + work_merge_offset(N, E));
+    g.keys = c.take<uint64_t>(align256(8 * (size_t)pow2_at_least(N)));
+    g.ws = c.take<uint8_t>(align256((size_t)N * E));
+    g.wr = c.take<uint8_t>(align256((size_t)N * E));
+    g.wm = c.take<int32_t>(align256(16 * (size_t)N));
+    g.source_offset = c.off;
+    g.source = c.take<int32_t>(256);
+    g.mkeys = c.take<uint64_t>(align256(8 * (size_t)N));
+    g.child.keys = c.take<uint64_t>(8 * (size_t)kSortTile);
+    g.child.flag = c.take<int32_t>(256);
+    g.child.sorted = c.take<uint64_t>(8 * (size_t)kSortTile);
+    g.bytes = c.off;
     return g;
 }
 
-void replace_scatter(int E, int N, const GaWork& w, uint8_t* ps, uint8_t* pr, int32_t* ph, int32_t* psc, uint8_t* pf,
-                     int32_t* pp, hipStream_t st) {
+void replace_move_rows(int E, int N, int base, const uint64_t* sorted, uint8_t* ps, uint8_t* pr, int32_t* ph,
+                       int32_t* psc, uint8_t* pf, int32_t* pp, const uint8_t* cs, const uint8_t* cr, const int32_t* ch,
+                       const int32_t* csc, const uint8_t* cf, const int32_t* cp, const GaWork& w, hipStream_t st) {
+    hipLaunchKernelGGL(replace_gather_kernel, dim3(N), dim3(64), 0, st, E, base, sorted, ps, pr, ph, psc, pf, pp, cs, cr,
+                       ch, csc, cf, cp, w.ws, w.wr, w.wm, w.source);
     hipLaunchKernelGGL(replace_scatter_kernel, dim3(N), dim3(64), 0, st, E, w.ws, w.wr, w.wm, ps, pr, ph, psc, pf, pp);
 }
 }  // namespace ttga
 
 extern "C" size_t tt_ga_work_bytes(int N, int E) {
     if (N < 1 || E < 1) return 0;
-    return work_merge_offset(N, E) + align256(8 * (size_t)N) + 16 * (size_t)kSortTile + 256;
+    return ga_work_layout(nullptr, N, E).bytes;
 }
 
 extern "C" size_t tt_ga_work_source_offset(int N, int E) {
     if (N < 1 || E < 1) return 0;
-    return work_source_offset(N, E);
+    return ga_work_layout(nullptr, N, E).source_offset;
 }
 
 extern "C" int tt_ga_replace(const tt_problem* p, uint8_t* pop_slot, uint8_t* pop_room, int32_t* pop_hcv,
@@ -526,42 +560,21 @@ extern "C" int tt_ga_replace(const tt_problem* p, uint8_t* pop_slot, uint8_t* po
     hipStream_t st = (hipStream_t)stream;
     const int E = p->E, NP = pow2_at_least(N);
     const GaWork gw = ga_work_layout(work, N, E);
-    uint64_t* keys = gw.keys;
-    const uint64_t* sorted = keys;
+    const uint64_t* sorted = gw.keys;
     // C = 0 sorts a population with no order to rely on (the initial sort,
     // ga.cpp:433-434): the multi-workgroup sort, not the merge path's
     // one-workgroup fallback (which a generation meets only when a migrant
     // survives out of order, C = 1)
     if (C > 0 && C <= kSortTile) {
-        uint64_t* mkeys = gw.mkeys;
-        uint64_t* ckeys = (uint64_t*)((uint8_t*)mkeys + align256(8 * (size_t)N));
-        int32_t* flag = (int32_t*)(ckeys + kSortTile);
-        const int CP = pow2_at_least(std::max(C, 2));
-        hipLaunchKernelGGL(replace_prep_kernel, dim3(kPrepBlocks), dim3(256), 0, st, pop_penalty, child_penalty, N, C, CP,
-                           ckeys, flag);
-        const uint64_t* csorted = ckeys;
-        if (use_rank_sort(CP)) {
-            uint64_t* cs2 = (uint64_t*)((uint8_t*)flag + 256);
-            sort_rank_tiles(ckeys, CP, st);
-            rank_scatter(ckeys, CP, cs2, st);
-            csorted = cs2;
-        } else {
-            sort_keys(ckeys, CP, st);
-        }
-        hipLaunchKernelGGL(replace_merge_kernel, dim3((N + 255) / 256), dim3(256), 0, st, pop_penalty, N, C, csorted,
-                           flag, mkeys);
-        hipLaunchKernelGGL(replace_fallback_sort_kernel, dim3(1), dim3(1024), 0, st, pop_penalty, child_penalty, C, keys,
-                           NP, flag, mkeys, N);
-        sorted = mkeys;
+        sorted = merge_sorted_keys(pop_penalty, N, ChildCount{C, nullptr}, child_penalty, N - C, padded(C), gw.child, gw,
+                                   st);
     } else {
         hipLaunchKernelGGL(replace_keys_kernel, dim3((NP + 255) / 256), dim3(256), 0, st, pop_penalty, child_penalty, N,
-                           C, NP, keys);
-        sort_keys(keys, NP, st);
+                           C, NP, gw.keys);
+        sort_keys(gw.keys, NP, st);
     }
-    hipLaunchKernelGGL(replace_gather_kernel, dim3(N), dim3(64), 0, st, E, N, C, sorted, pop_slot, pop_room, pop_hcv,
-                       pop_scv, pop_feasible, pop_penalty, child_slot, child_room, child_hcv, child_scv, child_feasible,
-                       child_penalty, gw.ws, gw.wr, gw.wm, gw.source);
-    replace_scatter(E, N, gw, pop_slot, pop_room, pop_hcv, pop_scv, pop_feasible, pop_penalty, st);
+    replace_move_rows(E, N, N - C, sorted, pop_slot, pop_room, pop_hcv, pop_scv, pop_feasible, pop_penalty, child_slot,
+                      child_room, child_hcv, child_scv, child_feasible, child_penalty, gw, st);
     return check_hip(hipGetLastError(), "tt_ga_replace launch");
 }
 
@@ -577,6 +590,9 @@ extern "C" int tt_lpt_order(const tt_problem* p, const int32_t* key, int n, int3
     const int NP = pow2_at_least(n);
     uint64_t* keys = (uint64_t*)work;
     hipLaunchKernelGGL(lpt_keys_kernel, dim3((NP + 255) / 256), dim3(256), 0, st, key, n, NP, keys);
+    // not sort_any: its sorted copy needs a second array of NP keys, which this call's
+    // work buffer (8 * pow2(n) bytes) does not have, and the order would take a third
+    // launch; the fused kernel writes the order from the ranks
     if (use_rank_sort(NP)) {
         const int NT = NP / kRankTile;
         sort_rank_tiles(keys, NP, st);

@@ -1,8 +1,9 @@
-// What tt_ga.hip's replacement shares with a replacement of another kind
-// (tt_unique.hip): the u64 key sorts, the survivors-in-order check, the layout
-// of the work buffer and the row movers. The kernels live in tt_ga.hip; this
-// header declares their host launchers and holds the small device helpers
-// both files inline.
+// What tt_ga_replace (tt_ga.hip) and tt_ga_replace_unique (tt_unique.hip) share:
+// the u64 key sorts, the merge form (order check, merge path, fallback sort), the
+// row movers and the carve of the work buffer. The kernels live in tt_ga.hip, once;
+// the two callers differ in two data items, the child count (ChildCount) and the
+// base of a child key's low word. This header declares the host launchers and
+// holds the small device helpers of these steps.
 #pragma once
 #include "tt_internal.h"
 
@@ -68,28 +69,75 @@ __device__ __forceinline__ void copy_rows2(uint8_t* __restrict__ d0, const uint8
     }
 }
 
-// ascending sort of NP (a power of two) u64 keys on stream st, in place
-void sort_keys(uint64_t* keys, int NP, hipStream_t st);
-// NP keys in [2*kRankTile, kSortTile]: sorted by tiles + ranks, in two steps:
-// sort_rank_tiles sorts the tiles in place, then a kernel that counts every
-// key's rank writes the result (rank_scatter: the sorted copy `out`)
-bool use_rank_sort(int NP);
-void sort_rank_tiles(uint64_t* keys, int NP, hipStream_t st);
-void rank_scatter(const uint64_t* keys, int NP, uint64_t* out, hipStream_t st);
+// How many children a replacement merges in: a host value, or (word non-null) a
+// device word written earlier on the stream (tt_ga_replace_unique's n_kept)
+struct ChildCount {
+    int value;
+    const int32_t* word;
+};
+__device__ __forceinline__ int child_count(const ChildCount& c) { return c.word ? *c.word : c.value; }
 
-// The parts of tt_ga_replace's work buffer (tt_ga_work_bytes(N, E)) that a
-// replacement of another kind shares: sort keys [pow2(N)], the gathered rows
-// and meta, the source word (tt_ga_work_source_offset) and the merged keys [N]
+// key i of the merged population: the survivors' (positions < k) and, behind them, ckeys
+__device__ __forceinline__ uint64_t merged_key(const int32_t* __restrict__ pen, const uint64_t* __restrict__ ckeys,
+                                               int N, int k, int i) {
+    return i >= N ? ~0ull : i < k ? sort_key(pen[i], i) : ckeys[i - k];
+}
+
+// child keys are padded with ~0 to a power of two >= 2
+inline int padded(int n) { return pow2_at_least(n > 2 ? n : 2); }
+
+// Consecutive regions of a work buffer; with a null buffer only the offsets count
+struct Carve {
+    uint8_t* base;
+    size_t off = 0;
+    template <class T>
+    T* take(size_t bytes) {
+        T* p = base ? (T*)(base + off) : nullptr;
+        off += bytes;
+        return p;
+    }
+};
+
+// The child side of the merge form: the child keys (padded), their sorted copy
+// when the tiles + ranks sort runs, and the survivors-in-order flags
+struct ChildWork {
+    uint64_t *keys, *sorted;
+    int32_t* flag;
+};
+
+// tt_ga_replace's work buffer: sort keys [pow2(N)], the gathered rows and meta, the
+// source word, the merged keys [N], and the child side of its merge form, of kSortTile
+// keys (tt_ga_replace_unique brings its own, of pow2(C) keys).
+// bytes = tt_ga_work_bytes(N, E), source_offset = tt_ga_work_source_offset
 struct GaWork {
     uint64_t* keys;
     uint8_t *ws, *wr;
     int32_t *wm, *source;
     uint64_t* mkeys;
+    ChildWork child;
+    size_t source_offset, bytes;
 };
 GaWork ga_work_layout(void* work, int N, int E);
 
-// the work rows and meta (GaWork ws, wr, wm) back into the population, N workgroups
-void replace_scatter(int E, int N, const GaWork& w, uint8_t* ps, uint8_t* pr, int32_t* ph, int32_t* psc, uint8_t* pf,
-                     int32_t* pp, hipStream_t st);
+// ascending sort of NP (a power of two) u64 keys on stream st, in place
+void sort_keys(uint64_t* keys, int NP, hipStream_t st);
+// the same, by whichever sort is fastest for NP; returns where the sorted keys are:
+// `keys`, or `other` (NP keys) when the tiles + ranks sort ran (2*kRankTile <= NP <= kSortTile)
+const uint64_t* sort_any(uint64_t* keys, uint64_t* other, int NP, hipStream_t st);
+
+// The merge form for 0 < C <= kSortTile: the survivors' order checked, the `count`
+// child keys (cw.keys, padded to CP; made here from cpen as sort_key(cpen[c], base + c)
+// when cpen is given) sorted, merged with the survivors or, those out of order, all
+// keys sorted by one workgroup (in w.keys). Returns the merged population's sorted
+// keys (w.mkeys).
+const uint64_t* merge_sorted_keys(const int32_t* pen, int N, ChildCount count, const int32_t* cpen, int base, int CP,
+                                  const ChildWork& cw, const GaWork& w, hipStream_t st);
+
+// Rows and meta in the order of `sorted` (a key's low word: a member's position
+// < base, or base + c for child c) through the work rows back into the population,
+// and the new pop[0]'s low word into the source word; 2 launches of N workgroups
+void replace_move_rows(int E, int N, int base, const uint64_t* sorted, uint8_t* ps, uint8_t* pr, int32_t* ph,
+                       int32_t* psc, uint8_t* pf, int32_t* pp, const uint8_t* cs, const uint8_t* cr, const int32_t* ch,
+                       const int32_t* csc, const uint8_t* cf, const int32_t* cp, const GaWork& w, hipStream_t st);
 
 }  // namespace ttga

@@ -24,14 +24,12 @@
 //   keep_scan     one workgroup: prefix sum over child_keep -> D = n_kept and
 //                 the kept children's penalty keys sort_key(penalty, N + c) in
 //                 child order, padded with ~0 to a power of two.
-//   then tt_ga_replace's merge form with k = N - D read from device memory:
-//   survivors' order checked (unique_prep), the kept keys sorted (one
-//   workgroup for C <= kSortTile), merged with the survivors (unique_merge) or,
-//   when a survivor is out of order, everything sorted by one workgroup
-//   (unique_fallback_sort); gather (N workgroups, the source word N + c for a
-//   child) and tt_ga.hip's scatter. C > kSortTile: a full key sort instead.
-#include <algorithm>
-
+//   then tt_ga_replace's own steps (tt_ga.hip's kernels through
+//   merge_sorted_keys and replace_move_rows, tt_replace_internal.h) with the two
+//   things that differ passed as data: the child count is the device word n_kept
+//   (the kernels that need k = N - D load it) and the base of a child key's low
+//   word is N, so the source word of a child is N + c. Only the key fill of the
+//   full sort for C > kSortTile is this file's own (unique_keys).
 #include "../../include/ttga_unique.h"
 #include "tt_replace_internal.h"
 
@@ -214,129 +212,54 @@ __global__ __launch_bounds__(1024) void keep_scan_kernel(const uint8_t* __restri
     if (t == 0) *n_kept = D;
 }
 
-// flag[g] = 1 when workgroup g's share of the survivors (positions < N - D) is in key order
-__global__ __launch_bounds__(256) void unique_prep_kernel(const int32_t* __restrict__ pen, int N,
-                                                          const int32_t* __restrict__ n_kept,
-                                                          int32_t* __restrict__ flag) {
-    const int k = N - *n_kept;
-    const int gt = blockIdx.x * blockDim.x + threadIdx.x, nth = gridDim.x * blockDim.x;
-    bool ok = true;
-    for (int i = gt; i + 1 < k; i += nth) ok &= (uint32_t)pen[i] <= (uint32_t)pen[i + 1];
-    ok = __syncthreads_and(ok);
-    if (threadIdx.x == 0) flag[blockIdx.x] = ok ? 1 : 0;
-}
-
-// merge path: output i takes the i-th smallest of the survivors (pen[a], a) and
-// the D sorted kept keys (tt_ga.hip's replace_merge_kernel with D from the device)
-__global__ void unique_merge_kernel(const int32_t* __restrict__ pen, int N, const int32_t* __restrict__ n_kept,
-                                    const uint64_t* __restrict__ ckeys, const int32_t* __restrict__ flag,
-                                    uint64_t* __restrict__ mkeys) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (!survivors_sorted(flag) || i >= N) return;
-    const int D = *n_kept, k = N - D;
-    int lo = max(0, i - D), hi = min(i, k);
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (sort_key(pen[mid], mid) < ckeys[i - 1 - mid]) lo = mid + 1;
-        else hi = mid;
-    }
-    const int a = lo, b = i - a;
-    const uint64_t ka = a < k ? sort_key(pen[a], a) : ~0ull, kb = b < D ? ckeys[b] : ~0ull;
-    mkeys[i] = ka < kb ? ka : kb;
-}
-
-// keys of the merged population: the survivors' and, behind them, the kept keys
-__device__ __forceinline__ uint64_t merged_key(const int32_t* __restrict__ pen, const uint64_t* __restrict__ ckeys,
-                                               int N, int k, int i) {
-    return i >= N ? ~0ull : i < k ? sort_key(pen[i], i) : ckeys[i - k];
-}
-
-// the fallback (a survivor out of order): everything sorted by one workgroup
-__global__ __launch_bounds__(1024) void unique_fallback_sort_kernel(const int32_t* __restrict__ pen,
-                                                                    const uint64_t* __restrict__ ckeys,
-                                                                    const int32_t* __restrict__ n_kept,
-                                                                    uint64_t* __restrict__ keys, int NP,
-                                                                    const int32_t* __restrict__ flag,
-                                                                    uint64_t* __restrict__ mkeys, int N) {
-    if (survivors_sorted(flag)) return;
-    const int k = N - *n_kept;
-    for (int i = threadIdx.x; i < NP; i += blockDim.x) keys[i] = merged_key(pen, ckeys, N, k, i);
-    __threadfence_block();
-    __syncthreads();
-    bitonic_global(keys, NP);
-    for (int i = threadIdx.x; i < N; i += blockDim.x) mkeys[i] = keys[i];
-}
-
-// C > kSortTile: the keys of a full sort
+// C > kSortTile: the keys of a full sort. The one step not shared with tt_ga_replace,
+// which has no child-key array of that size and fills its keys from the penalties
 __global__ void unique_keys_kernel(const int32_t* __restrict__ pen, const uint64_t* __restrict__ ckeys,
                                    const int32_t* __restrict__ n_kept, int N, int NP, uint64_t* __restrict__ keys) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < NP) keys[i] = merged_key(pen, ckeys, N, N - *n_kept, i);
 }
 
-// gather the sorted population into the work rows (one wave per row); a key's
-// low word is a member's position (< N) or N + the child's index
-__global__ __launch_bounds__(64) void unique_gather_kernel(int E, int N, const uint64_t* __restrict__ keys,
-                                                           const uint8_t* __restrict__ ps, const uint8_t* __restrict__ pr,
-                                                           const int32_t* __restrict__ ph, const int32_t* __restrict__ psc,
-                                                           const uint8_t* __restrict__ pf, const int32_t* __restrict__ pp,
-                                                           const uint8_t* __restrict__ cs, const uint8_t* __restrict__ cr,
-                                                           const int32_t* __restrict__ ch, const int32_t* __restrict__ csc,
-                                                           const uint8_t* __restrict__ cf, const int32_t* __restrict__ cp,
-                                                           uint8_t* __restrict__ ws, uint8_t* __restrict__ wr,
-                                                           int32_t* __restrict__ wm, int32_t* __restrict__ best_src) {
-    const int i = blockIdx.x;
-    const int src = (int)(keys[i] & 0xFFFFFFFFu);
-    if (i == 0 && threadIdx.x == 0) *best_src = src;
-    const bool child = src >= N;
-    const int r = child ? src - N : src;
-    const uint8_t* s = (child ? cs : ps) + (long)r * E;
-    const uint8_t* m = (child ? cr : pr) + (long)r * E;
-    copy_rows2(ws + (long)i * E, s, wr + (long)i * E, m, E, threadIdx.x);
-    if (threadIdx.x == 0) {
-        wm[4 * i + 0] = child ? ch[r] : ph[r];
-        wm[4 * i + 1] = child ? csc[r] : psc[r];
-        wm[4 * i + 2] = child ? cf[r] : pf[r];
-        wm[4 * i + 3] = child ? cp[r] : pp[r];
-    }
-}
-
-// the sorted form of NP keys (a power of two >= 2) with tt_ga.hip's sorts:
-// `keys` in place, or `other` when the tiles + ranks sort ran
-static const uint64_t* sort_any(uint64_t* keys, uint64_t* other, int NP, hipStream_t st) {
-    if (use_rank_sort(NP)) {
-        sort_rank_tiles(keys, NP, st);
-        rank_scatter(keys, NP, other, st);
-        return other;
-    }
-    sort_keys(keys, NP, st);
-    return keys;
-}
-
 static bool hash_bits_ok(int hash_bits) { return hash_bits >= 0 && hash_bits <= 31; }
 static uint32_t hash_mask(int hash_bits) { return hash_bits == 0 ? 0xFFFFFFFFu : (1u << hash_bits) - 1u; }
-
-static int padded(int n) { return pow2_at_least(std::max(n, 2)); }
 
 // work of tt_ga_replace_unique behind tt_ga_replace's: child hash keys [CP] u64 |
 // their sorted copy [CP] | kept penalty keys [CP] | their sorted copy [CP] |
 // member hashes [N] u32 | survivors-in-order flags (256 B)
+// (bytes: all of tt_ga_unique_work_bytes(N, C, E))
 struct UniqueWork {
-    uint64_t *hkeys, *hsorted, *ckeys, *csorted;
+    uint64_t *hkeys, *hsorted;
+    ChildWork child;
     uint32_t* phash;
-    int32_t* flag;
+    size_t bytes;
 };
 static UniqueWork unique_work_layout(void* work, int N, int C, int E) {
     const size_t kb = align256(8 * (size_t)padded(C));
-    uint8_t* w = (uint8_t*)work + tt_ga_work_bytes(N, E);
+    Carve c{(uint8_t*)work, ga_work_layout(nullptr, N, E).bytes};
     UniqueWork u;
-    u.hkeys = (uint64_t*)w;
-    u.hsorted = (uint64_t*)(w + kb);
-    u.ckeys = (uint64_t*)(w + 2 * kb);
-    u.csorted = (uint64_t*)(w + 3 * kb);
-    u.phash = (uint32_t*)(w + 4 * kb);
-    u.flag = (int32_t*)(w + 4 * kb + align256(4 * (size_t)N));
+    u.hkeys = c.take<uint64_t>(kb);
+    u.hsorted = c.take<uint64_t>(kb);
+    u.child.keys = c.take<uint64_t>(kb);
+    u.child.sorted = c.take<uint64_t>(kb);
+    u.phash = c.take<uint32_t>(align256(4 * (size_t)N));
+    u.child.flag = c.take<int32_t>(256);
+    u.bytes = c.off;
     return u;
+}
+
+// work of tt_genome_first: the P hash keys, padded | their sorted copy
+struct GenomeWork {
+    uint64_t *keys, *other;
+    size_t bytes;
+};
+static GenomeWork genome_work_layout(void* work, int P) {
+    const size_t kb = align256(8 * (size_t)padded(P));
+    Carve c{(uint8_t*)work};
+    GenomeWork g;
+    g.keys = c.take<uint64_t>(kb);
+    g.other = c.take<uint64_t>(kb);
+    g.bytes = c.off;
+    return g;
 }
 
 }  // namespace ttga
@@ -345,7 +268,7 @@ using namespace ttga;
 
 extern "C" size_t tt_genome_work_bytes(int P, int E) {
     if (P < 1 || E < 1) return 0;
-    return 2 * align256(8 * (size_t)padded(P));
+    return genome_work_layout(nullptr, P).bytes;
 }
 
 extern "C" int tt_genome_first(const tt_problem* p, const uint8_t* slot, const uint8_t* room, int P, int32_t* first,
@@ -359,12 +282,11 @@ extern "C" int tt_genome_first(const tt_problem* p, const uint8_t* slot, const u
     if ((rc = use_device(p))) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int E = p->E, PP = padded(P);
-    uint64_t* keys = (uint64_t*)work;
-    uint64_t* other = (uint64_t*)((uint8_t*)work + align256(8 * (size_t)PP));
+    const GenomeWork gw = genome_work_layout(work, P);
     hipLaunchKernelGGL(hash_rows_kernel, dim3((P + kHashRows - 1) / kHashRows), dim3(256), 0, st, E, (const uint8_t*)nullptr,
-                       (const uint8_t*)nullptr, 0, slot, room, P, hash_mask(hash_bits), (uint32_t*)nullptr, keys, PP,
+                       (const uint8_t*)nullptr, 0, slot, room, P, hash_mask(hash_bits), (uint32_t*)nullptr, gw.keys, PP,
                        (uint8_t*)nullptr);
-    const uint64_t* sorted = sort_any(keys, other, PP, st);
+    const uint64_t* sorted = sort_any(gw.keys, gw.other, PP, st);
     hipLaunchKernelGGL(unique_probe_kernel, dim3((P + 255) / 256), dim3(256), 0, st, E, (const uint8_t*)nullptr,
                        (const uint8_t*)nullptr, (const uint32_t*)nullptr, 0, slot, room, sorted, P, (uint8_t*)nullptr,
                        first);
@@ -373,7 +295,7 @@ extern "C" int tt_genome_first(const tt_problem* p, const uint8_t* slot, const u
 
 extern "C" size_t tt_ga_unique_work_bytes(int N, int C, int E) {
     if (N < 1 || C < 0 || E < 1) return 0;
-    return tt_ga_work_bytes(N, E) + 4 * align256(8 * (size_t)padded(C)) + align256(4 * (size_t)N) + 256;
+    return unique_work_layout(nullptr, N, C, E).bytes;
 }
 
 extern "C" int tt_ga_replace_unique(const tt_problem* p, uint8_t* pop_slot, uint8_t* pop_room, int32_t* pop_hcv,
@@ -413,27 +335,17 @@ extern "C" int tt_ga_replace_unique(const tt_problem* p, uint8_t* pop_slot, uint
                        (const uint8_t*)pop_room, (const uint32_t*)uw.phash, N, child_slot, child_room, hsorted, C,
                        child_keep, (int32_t*)nullptr);
     hipLaunchKernelGGL(keep_scan_kernel, dim3(1), dim3(1024), 0, st, (const uint8_t*)child_keep, child_penalty, N, C, CP,
-                       uw.ckeys, n_kept);
-    // tt_ga_replace with the D = *n_kept kept children
-    const uint64_t* sorted = gw.mkeys;
+                       uw.child.keys, n_kept);
+    // tt_ga_replace's steps with the D = *n_kept kept children, their keys' low words N + c
+    const uint64_t* sorted = gw.keys;
     if (C <= kSortTile) {
-        hipLaunchKernelGGL(unique_prep_kernel, dim3(kPrepBlocks), dim3(256), 0, st, (const int32_t*)pop_penalty, N,
-                           (const int32_t*)n_kept, uw.flag);
-        const uint64_t* csorted = sort_any(uw.ckeys, uw.csorted, CP, st);
-        hipLaunchKernelGGL(unique_merge_kernel, dim3((N + 255) / 256), dim3(256), 0, st, (const int32_t*)pop_penalty, N,
-                           (const int32_t*)n_kept, csorted, (const int32_t*)uw.flag, gw.mkeys);
-        hipLaunchKernelGGL(unique_fallback_sort_kernel, dim3(1), dim3(1024), 0, st, (const int32_t*)pop_penalty, csorted,
-                           (const int32_t*)n_kept, gw.keys, NP, (const int32_t*)uw.flag, gw.mkeys, N);
+        sorted = merge_sorted_keys(pop_penalty, N, ChildCount{0, n_kept}, nullptr, N, CP, uw.child, gw, st);
     } else {
         hipLaunchKernelGGL(unique_keys_kernel, dim3((NP + 255) / 256), dim3(256), 0, st, (const int32_t*)pop_penalty,
-                           (const uint64_t*)uw.ckeys, (const int32_t*)n_kept, N, NP, gw.keys);
+                           (const uint64_t*)uw.child.keys, (const int32_t*)n_kept, N, NP, gw.keys);
         sort_keys(gw.keys, NP, st);
-        sorted = gw.keys;
     }
-    hipLaunchKernelGGL(unique_gather_kernel, dim3(N), dim3(64), 0, st, E, N, sorted, (const uint8_t*)pop_slot,
-                       (const uint8_t*)pop_room, (const int32_t*)pop_hcv, (const int32_t*)pop_scv,
-                       (const uint8_t*)pop_feasible, (const int32_t*)pop_penalty, child_slot, child_room, child_hcv,
-                       child_scv, child_feasible, child_penalty, gw.ws, gw.wr, gw.wm, gw.source);
-    replace_scatter(E, N, gw, pop_slot, pop_room, pop_hcv, pop_scv, pop_feasible, pop_penalty, st);
+    replace_move_rows(E, N, N, sorted, pop_slot, pop_room, pop_hcv, pop_scv, pop_feasible, pop_penalty, child_slot,
+                      child_room, child_hcv, child_scv, child_feasible, child_penalty, gw, st);
     return check_hip(hipGetLastError(), "tt_ga_replace_unique launch");
 }

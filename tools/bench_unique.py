@@ -2,7 +2,7 @@
 shape (comp01, population 65,536, 8,192 children by default):
 
     python tools/bench_unique.py [--config comp01] [--pop 65536] [--children 8192]
-                                 [--launches 200] [--repeats 5] [--out FILE]
+                                 [--launches 200] [--repeats 5] [--out FILE] [--lib path]
 
 From one saved population (evaluated and sorted, as a previous replacement
 leaves it) and two saved sets of evaluated children -- one with no duplicate,
@@ -51,7 +51,10 @@ def main():
     ap.add_argument("--launches", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--out", default=str(REPO / "profiles" / "unique_bench.json"))
+    ap.add_argument("--lib", default=None)
     a = ap.parse_args()
+    if a.lib:
+        native._lib = native.load(pathlib.Path(a.lib).resolve())
     inst = ttga.config_instance(a.config)
     dp = native.DeviceProblem(inst)
     N, C, E = a.pop, a.children, inst.E
