@@ -59,7 +59,8 @@
  *   67,108,863 (one wave a row)     those seven with at most 16 rooms,
  *                tt_mutation, tt_local_search*, tt_ga_replace,
  *                tt_ga_replace_unique, tt_kempe_move, tt_slot_swap, tt_lahc,
- *                tt_lahc_kempe, tt_lahc_kempe_aug, tt_lahc_multi;
+ *                tt_lahc_kempe, tt_lahc_kempe_aug, tt_lahc_multi, tt_move1_scan,
+ *                tt_move1_descent;
  *   268,435,440  tt_genome_first, with 16 rows to a workgroup of 256;
  *   536,870,848 or more  tt_eval's tile kernels (7, 8: a workgroup of 256 or
  *                512 threads per 64 rows, or a grid that does not grow with P).
@@ -76,9 +77,12 @@
  * keep hcv 0, the best row seen comes back; it brings in ttga_lahc_kempe.h,
  * the same walk with Kempe chains among its candidates, and ttga_lahc_kempe_aug.h, which
  * finds those chains' rooms by augmenting paths, and ttga_lahc_multi.h, which runs
- * several such walks from every row and keeps the best) and ttga_cx.h (a conflict-guided
+ * several such walks from every row and keeps the best), ttga_cx.h (a conflict-guided
  * crossover: each event takes the parent's slot that clashes less with what
- * the child holds already, and a breed call built on it).
+ * the child holds already, and a breed call built on it) and ttga/move1.h (the
+ * full single-event neighbourhood of a feasible row: what every "event e goes
+ * to slot t" costs and which room it takes, and the steepest descent on that
+ * table; it sits in include/ttga/, included as "ttga/move1.h").
  */
 #ifndef TTGA_H
 #define TTGA_H
@@ -293,7 +297,9 @@ int tt_ga_replace(const tt_problem* p, uint8_t* pop_slot, uint8_t* pop_room, int
  *   bit 8 (256) ttga_lahc.h's tt_lahc or tt_lahc_kempe left a row with a slot
  *              gene >= 45 or a room gene >= R untouched;
  *   bit 9 (512) ttga_cx.h's tt_crossover_guided or tt_ga_breed_guided skipped an
- *              order entry outside 0..E-1.
+ *              order entry outside 0..E-1;
+ *   bit 10 (1024) ttga/move1.h's tt_move1_scan or tt_move1_descent left a row with
+ *              a slot gene >= 45 or a room gene >= R unscanned.
  * Synchronises the device. */
 int tt_device_status(const tt_problem* p, int32_t* status);
 

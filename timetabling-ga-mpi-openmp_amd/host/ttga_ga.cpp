@@ -14,7 +14,7 @@
 //           [--report] [--unique] [--init random|greedy] [--kempe P] [--kempe-max-chain N]
 //           [--slot-swap N] [--lahc N] [--lahc-history L] [--lahc-swap P]
 //           [--lahc-kempe P] [--lahc-kempe-max-chain N] [--lahc-kempe-rooms direct|augment]
-//           [--lahc-walkers K]
+//           [--lahc-walkers K] [--move1-descent N]
 //           [--crossover uniform|guided] [--crossover-repair]
 //
 // --crossover guided: every sub-batch is bred by tt_ga_breed_guided
@@ -55,6 +55,16 @@
 // {"lahcWalkers": {"gain", "gainFirst", "rows", "walkers", "winnerLater"}} line after them
 // (ttga.islands prints the same): the rows that walked, the winners' gain, walker 0's gain
 // on the same rows (the single walk's) and the rows another walker won.
+//
+// --move1-descent N: tt_move1_descent (include/ttga/move1.h) with max_passes N runs
+// directly behind every tt_local_search_eval, and behind tt_slot_swap and the walk
+// where those are on, on the same stream: on every sub-batch of children, on the
+// members before the initial sort. On every feasible row the feasible single-event
+// move that lowers scv most is applied, at most N times, and the rows' scv and
+// penalty are lowered in place. Each island then prints one {"move1Descent":
+// {"gain", "improved", "meanPasses", "rows"}} line after the lahc, lahcKempe and
+// lahcWalkers lines and before any report line (ttga.islands prints the same). The
+// default is 0: no call.
 //
 // --slot-swap N: tt_slot_swap (include/ttga_slotswap.h) with max_passes N runs
 // directly behind every tt_local_search_eval, on the same stream, and lowers
@@ -137,6 +147,7 @@
 #include "../../include/ttga_lahc.h"
 #include "../../include/ttga_cx.h"
 #include "../../include/ttga_unique.h"
+#include "../../include/ttga/move1.h"
 
 namespace {
 
@@ -176,6 +187,7 @@ struct Stages {
     int lahc_walkers = 1;                         // --lahc-walkers: tt_lahc_multi's walkers (1: the calls above)
     bool guided = false;                          // --crossover guided: tt_ga_breed_guided breeds
     bool cx_repair = false;                       // --crossover-repair
+    int move1_descent = 0;                        // --move1-descent: tt_move1_descent's max_passes (0: never called)
 };
 
 struct Control {
@@ -273,6 +285,7 @@ Control parse_control(int argc, char** argv) {
     if (s.lahc_walkers > 1024) bad_flag("--lahc-walkers must be an integer from 1 to 1024");
     s.cx_repair = take_flag(args, "--crossover-repair");
     take_choice(args, "--crossover", "uniform", "guided", "--crossover must be uniform or guided", s.guided);
+    take_int(args, "--move1-descent", 0, "--move1-descent must be a non-negative integer", s.move1_descent);
     if (s.cx_repair && !s.guided) bad_flag("--crossover-repair needs --crossover guided");
     if (s.lahc_kempe > 0 && s.lahc <= 0) bad_flag("--lahc-kempe needs --lahc");
     if (s.lahc_kempe > 0 && !(s.lahc_swap <= 1.0 - s.lahc_kempe))         // tt_lahc_kempe's own test
@@ -720,6 +733,7 @@ struct Island {
     RunLog<7> lk_log;
     int lk_width() const { return stage.lahc_kempe_augment || stage.lahc_walkers > 1 ? 7 : 5; }
     RunLog<2> lw_log;                                 // --lahc-walkers: every searched row's winner and walker 0's gain
+    RunLog<2> m1_log;                                 // --move1-descent: every searched row's gain and passes
     RunLog<2> cx_log;                                 // --crossover guided: every child's cost, repaired and flags
     int32_t* ev_order = nullptr;                      // event_order()'s, once computed
 
@@ -768,6 +782,7 @@ struct Island {
         if (stage.lahc > 0) lahc_log.alloc(N + bred, "late-acceptance rows", true);       // the members too
         if (stage.lahc_kempe > 0) lk_log.alloc(N + bred, "late-acceptance rows");
         if (stage.lahc_walkers > 1) lw_log.alloc(N + bred, "late-acceptance rows");
+        if (stage.move1_descent > 0) m1_log.alloc(N + bred, "single-event descent rows");  // the members too
         if (stage.guided) {
             cx_log.alloc(bred, "guided crossovers", true);
             event_order();                            // before any part's stream breeds in it
@@ -823,6 +838,7 @@ struct Island {
                  "tt_local_search_eval");
         if (stage.slot_swap > 0) swap_slots(pop, st);
         if (stage.lahc > 0) late_acceptance(pop, rng_init, st);
+        if (stage.move1_descent > 0) descend_move1(pop, st);
         if (stage.unique)
             check_tt(tt_ga_replace_unique(tp, pop.slot, pop.room, pop.hcv, pop.scv, pop.feasible, pop.penalty, N,
                                           pop.slot, pop.room, pop.hcv, pop.scv, pop.feasible, pop.penalty, 0, nullptr,
@@ -945,6 +961,32 @@ struct Island {
         k.obj["gain"] = Json::I(total);
         k.obj["meanPasses"] = Json::D(improved ? (double)passes / (double)improved : 0.0);
         return wrap("slotSwap", k);
+    }
+
+    // --move1-descent: the single-event steepest descent on the searched rows r on s, behind
+    // their search, evaluation, timeslot swap and walk; their scv and penalty are lowered in place
+    void descend_move1(const Pop& r, hipStream_t s) {
+        const long at = m1_log.reserve(r.n);
+        check_tt(tt_move1_descent(tp, r.slot, r.room, r.n, stage.move1_descent, r.scv, r.penalty, m1_log.col(0) + at,
+                                  m1_log.col(1) + at, s),
+                 "tt_move1_descent");
+    }
+
+    // the --move1-descent line (ttga/ga.py move1_descent_line)
+    Json move1_descent_report() {
+        const auto h = read(m1_log);
+        long improved = 0, passes = 0, total = 0;
+        for (long i = 0; i < h.rows; i++) {
+            improved += h.col[1][i] > 0;
+            passes += h.col[1][i];
+            total += h.col[0][i];
+        }
+        Json k;
+        k.obj["rows"] = Json::I(h.rows);
+        k.obj["improved"] = Json::I(improved);
+        k.obj["gain"] = Json::I(total);
+        k.obj["meanPasses"] = Json::D(improved ? (double)passes / (double)improved : 0.0);
+        return wrap("move1Descent", k);
     }
 
     // --lahc: the late-acceptance walk of the searched rows r (streams g) on s, behind their
@@ -1120,6 +1162,7 @@ struct Island {
         search(p.off, p.n, p.s, p.work);
         if (stage.slot_swap > 0) swap_slots(child_rows(p.off, p.n), p.s);
         if (stage.lahc > 0) late_acceptance(child_rows(p.off, p.n), rng_child + p.off, p.s);
+        if (stage.move1_descent > 0) descend_move1(child_rows(p.off, p.n), p.s);
         pending.push_back(j);
         if ((int)pending.size() >= parts) replace_oldest();
     }
@@ -1240,6 +1283,7 @@ struct Island {
         lahc_log.release();
         lk_log.release();
         lw_log.release();
+        m1_log.release();
         cx_log.release();
         for (size_t j = 0; j < part.size(); j++) {
             if (part[j].work) (void)hipFree(part[j].work);
@@ -1435,6 +1479,7 @@ int main(int argc, char** argv) {
     each_island(ctl.stage.lahc > 0, [](Island& I, int) { return I.lahc_report(); });
     each_island(ctl.stage.lahc_kempe > 0, [](Island& I, int) { return I.lahc_kempe_report(); });
     each_island(ctl.stage.lahc_walkers > 1, [](Island& I, int) { return I.lahc_walkers_report(); });
+    each_island(ctl.stage.move1_descent > 0, [](Island& I, int) { return I.move1_descent_report(); });
     each_island(ctl.report, [](Island& I, int k) { return I.report(k, k); });
     out.line(run_final_line(K, C, seconds_since(t_start)));
     for (int k = 0; k < K; k++) {

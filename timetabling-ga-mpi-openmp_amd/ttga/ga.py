@@ -22,6 +22,9 @@ kernels (include/ttga.h):
 * optionally (Island(lahc=N)) every searched row that is feasible then walks N
   late-acceptance steps over feasible rows (tt_lahc) and comes back as the best
   row of the walk: an addition too, which lowers scv only;
+* optionally (Island(move1_descent=N)) every searched row that is feasible then
+  takes at most N steps of steepest descent over its single-event moves
+  (tt_move1_descent): an addition too, which lowers scv only;
 * optionally (Island(crossover="guided")) the children are bred with the
   conflict-guided crossover (tt_ga_breed_guided) in place of the reference's
   uniform one: an addition too, which changes only how a crossed child's
@@ -185,6 +188,7 @@ _TALLIED = {
     "lahc_walkers": ("lahc_walkers > 1", None, ("winner", "walker_gain"), ("rows", "gain", "gainFirst", "winnerLater"),
                      True),
     "cx": ("crossover='guided'", "children", ("cost", "repaired"), ("crossed", "clean", "cost", "repaired"), False),
+    "move1_descent": ("move1_descent > 0", "rows", ("gain", "passes"), ("improved", "passes", "gain"), True),
 }
 
 
@@ -303,8 +307,18 @@ class Island(Members):
     slot of least cost. Everything else is unchanged. crossover="uniform"
     issues no new call at all. cx_stats() reports what the crossovers did.
 
+    move1_descent=n >= 1: tt_move1_descent(max_passes=n) (include/ttga/move1.h)
+    runs on the part's stream directly behind every tt_local_search_eval, and
+    behind tt_slot_swap and the walk where those are on -- on the children of
+    a sub-batch, on the members in initialize() before the sort. Only rows that
+    are feasible descend: the feasible single-event move that lowers scv most
+    is applied, at most n times, and their scv and penalty tensors are lowered
+    in place. It draws no random numbers. move1_descent=0 issues no call at
+    all. move1_descent_stats() reports what the descents did.
+
     `on` is the set of these stages that are on: "unique", "kempe",
-    "slot_swap", "lahc", "lahc_kempe", "cx" (the {stage}_stats() that do not raise).
+    "slot_swap", "lahc", "lahc_kempe", "cx", "move1_descent" (the
+    {stage}_stats() that do not raise).
     """
 
     def __init__(self, dp, pop_size: int = 10, children: int = 1, max_steps: int = 200, seed: int = 1,
@@ -315,7 +329,7 @@ class Island(Members):
                  lahc: int = 0, lahc_history: int = 500, lahc_swap: float = 0.5,
                  crossover: str = "uniform", crossover_repair: bool = False,
                  lahc_kempe: float = 0.0, lahc_kempe_max_chain: int = 0, lahc_kempe_rooms: str = "direct",
-                 lahc_walkers: int = 1):
+                 lahc_walkers: int = 1, move1_descent: int = 0):
         """stream: a torch.cuda.Stream of the island's own, or None (torch's current
         stream). Islands multiplexed on one GPU (ttga.islands --islands K) each take
         one, so one island's launches fill the SIMD slots another's local-search tail
@@ -323,7 +337,7 @@ class Island(Members):
         synchronises its stream first, and a caller that moves data between islands
         (migration) synchronises the device around it."""
         validate(init, kempe, kempe_max_chain, slot_swap, lahc, lahc_history, lahc_swap, crossover, crossover_repair,
-                 lahc_kempe, lahc_kempe_max_chain, lahc_kempe_rooms, lahc_walkers)
+                 lahc_kempe, lahc_kempe_max_chain, lahc_kempe_rooms, lahc_walkers, move1_descent)
         import torch
         if not (1 <= children <= pop_size):
             raise ValueError("need 1 <= children <= pop_size")
@@ -352,6 +366,7 @@ class Island(Members):
         self.lahc_kempe, self.lahc_kempe_max_chain = float(lahc_kempe), int(lahc_kempe_max_chain)
         self.lahc_kempe_rooms = lahc_kempe_rooms
         self.lahc_walkers = int(lahc_walkers)
+        self.move1_descent = int(move1_descent)
         self.crossover, self.crossover_repair = crossover, bool(crossover_repair)
         self.generation = 0
         self.schedule = schedule
@@ -394,7 +409,8 @@ class Island(Members):
                                            ("slot_swap", self.slot_swap > 0), ("lahc", self.lahc > 0),
                                            ("lahc_kempe", self.lahc_kempe > 0),
                                            ("lahc_walkers", self.lahc_walkers > 1),
-                                           ("cx", self.crossover == "guided")) if on}
+                                           ("cx", self.crossover == "guided"),
+                                           ("move1_descent", self.move1_descent > 0)) if on}
         self._init_tally = {}
         for stage, (_, _, outputs, _, in_init) in _TALLIED.items():
             if stage in self.on:
@@ -534,6 +550,8 @@ class Island(Members):
                 self._slot_swap(p, self._init_tally["slot_swap"])
             if self.lahc > 0:
                 self._lahc(p, self.rng_init, self._init_tally)
+            if self.move1_descent > 0:
+                self._move1_descent(p, self._init_tally["move1_descent"])
             if self.unique:
                 self.dp.ga_replace_unique(p, None, self.work, n_kept=self._init_kept)
             else:
@@ -585,6 +603,8 @@ class Island(Members):
                 self._slot_swap(p.child, p.tally["slot_swap"])
             if self.lahc > 0:
                 self._lahc(p.child, p.rng, p.tally)
+            if self.move1_descent > 0:
+                self._move1_descent(p.child, p.tally["move1_descent"])
             self._pending.append(j)
             if len(self._pending) >= self.parts:
                 self._replace_oldest()
@@ -612,10 +632,21 @@ class Island(Members):
         """tt_slot_swap on the searched rows (on the current stream, behind
         their search and evaluation) and its counts, summed on the device
         behind the call."""
+        self._descent(t, rows, lambda **out: self.dp.slot_swap(rows["slot"], self.slot_swap, **out))
+
+    @staticmethod
+    def _descent(t, rows, call):
+        """A descent that credits scv and penalty in place and reports gain and
+        passes a row: call(scv=, penalty=, gain=, passes=), then the tally's
+        rows, rows improved, passes and gain."""
         gain, passes = t.out["gain"], t.out["passes"]
-        self.dp.slot_swap(rows["slot"], self.slot_swap, scv=rows["scv"], penalty=rows["penalty"], gain=gain,
-                          passes=passes)
+        call(scv=rows["scv"], penalty=rows["penalty"], gain=gain, passes=passes)
         t.add(int(rows["slot"].shape[0]), (passes > 0).sum(), passes.sum(), gain.sum())
+
+    def _move1_descent(self, rows, t):
+        """tt_move1_descent on the searched rows, behind their search,
+        evaluation, timeslot swap and walk; counted as _slot_swap's."""
+        self._descent(t, rows, lambda **out: self.dp.move1_descent(rows["slot"], rows["room"], self.move1_descent, **out))
 
     def _lahc(self, rows, rng, tally):
         """tt_lahc, or with lahc_kempe > 0 tt_lahc_kempe (tt_lahc_kempe_aug
@@ -712,6 +743,15 @@ class Island(Members):
         """Island(slot_swap > 0): the rows tt_slot_swap was called on, how many
         of them it improved, the swaps applied and the scv gained in all."""
         return self._stats("slot_swap")
+
+    def move1_descent_stats(self) -> dict:
+        """Island(move1_descent > 0): the `rows` tt_move1_descent was called on,
+        how many of them it `improved`, `meanPasses`: the moves applied per
+        improved row (0 when there is none) and the scv gained in all."""
+        st = self._stats("move1_descent")
+        improved = st["improved"]
+        return {"rows": st["rows"], "improved": improved,
+                "meanPasses": float(st["passes"]) / improved if improved else 0.0, "gain": st["gain"]}
 
     def kempe_stats(self) -> dict:
         """Island(kempe > 0): the children tt_kempe_move was called on, how many
@@ -920,6 +960,12 @@ def slot_swap_line(stats: dict) -> str:
                                    "rows": int(stats["rows"])}})
 
 
+def move1_descent_line(stats: dict) -> str:
+    """The drivers' --move1-descent line of one island: Island.move1_descent_stats()."""
+    return json_line({"move1Descent": {"gain": int(stats["gain"]), "improved": int(stats["improved"]),
+                                       "meanPasses": float(stats["meanPasses"]), "rows": int(stats["rows"])}})
+
+
 def lahc_line(stats: dict) -> str:
     """The drivers' --lahc line of one island: Island.lahc_stats()."""
     return json_line({"lahc": {k: int(stats[k]) for k in ("accepted", "gain", "improved", "rows", "searched")}})
@@ -968,4 +1014,5 @@ STAGE_LINES = (
     ("lahc", False, lambda isl, proc, k: lahc_line(isl.lahc_stats())),
     ("lahc_kempe", False, lambda isl, proc, k: lahc_kempe_line(isl.lahc_kempe_stats())),
     ("lahc_walkers", False, lambda isl, proc, k: lahc_walkers_line(isl.lahc_walkers_stats())),
+    ("move1_descent", False, lambda isl, proc, k: move1_descent_line(isl.move1_descent_stats())),
 )

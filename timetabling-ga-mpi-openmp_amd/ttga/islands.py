@@ -55,6 +55,15 @@ Reference correspondence:
   after the lahc lines: the rows that walked, the walkers, the winners' gain,
   walker 0's gain on the same rows and the rows another walker won; the
   default is 1, which issues no new call),
+  `--move1-descent N` (tt_move1_descent, include/ttga/move1.h, with max_passes
+  N behind every local search, timeslot swap and walk,
+  ttga.ga.Island(move1_descent=N): on every feasible row the feasible
+  single-event move that lowers scv most is applied, at most N times; each
+  island then prints a `move1Descent` line after the lahc, lahcKempe and
+  lahcWalkers lines and before any report line -- the order of the stage
+  lines is crossover, kempe (behind each solution), then unique, slotSwap,
+  lahc, lahcKempe, lahcWalkers, move1Descent, then report:
+  rows, rows improved, mean moves per improved row, scv gained; 0: no call),
   `--crossover uniform|guided` / `--crossover-repair` (guided: the children are
   bred by tt_ga_breed_guided, include/ttga_cx.h, ttga.ga.Island(crossover=
   "guided", crossover_repair=...); each island then prints a `crossover` line

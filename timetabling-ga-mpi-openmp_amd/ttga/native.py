@@ -60,6 +60,10 @@ MAX_WALKERS = 1024                          # tt_lahc_multi's walkers: 1 .. 1024
 # include/ttga_cx.h
 CX_EXPORTS = ("tt_crossover_guided", "tt_ga_breed_guided")
 
+# include/ttga/move1.h
+MOVE1_EXPORTS = ("tt_move1_scan", "tt_move1_descent")
+MOVE1_CLASH, MOVE1_NO_ROOM, MOVE1_UNSCANNED, MOVE1_NONE = 255, 254, 253, 0x7FFFFFFF
+
 _lib = None
 
 
@@ -144,6 +148,10 @@ def load(path: os.PathLike | str | None = None) -> ctypes.CDLL:
     lib.tt_crossover_guided.restype = ctypes.c_int
     lib.tt_ga_breed_guided.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, dbl, dbl, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.tt_ga_breed_guided.restype = ctypes.c_int
+    lib.tt_move1_scan.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
+    lib.tt_move1_scan.restype = ctypes.c_int
+    lib.tt_move1_descent.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    lib.tt_move1_descent.restype = ctypes.c_int
     for name in EXPORTS:
         if name not in ("tt_last_error", "tt_ga_work_bytes", "tt_ga_work_source_offset"):
             getattr(lib, name).restype = ctypes.c_int
@@ -218,11 +226,12 @@ class DeviceProblem:
 
     # -- population operations (torch tensors on this device) -------------------
     @staticmethod
-    def _stream(t):
+    def _stream(t, stream=None):
         # note: every library call makes the handle's device current (hipSetDevice)
         # and leaves it so; tensors of another device are rejected by _pop/_rng
         import torch
-        return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+        st = torch.cuda.current_stream(t.device) if stream is None else stream
+        return ctypes.c_void_p(st.cuda_stream)
 
     def _pop(self, slot, room=None):
         import torch
@@ -651,6 +660,39 @@ class DeviceProblem:
             rng.data_ptr(), C, float(p_cross), float(p_mut), int(bool(skip_init_draws)), int(bool(repair)),
             child_slot.data_ptr(), child_room.data_ptr(), child_flags.data_ptr(), _ptr(cost), _ptr(repaired),
             self._stream(pop_slot)))
+
+    # -- the single-event neighbourhood (include/ttga/move1.h) ---------------------------
+    def move1_scan(self, slot, room, summary=None, d_scv=None, to_room=None, stream=None):
+        """tt_move1_scan on slot, room [P, E], which it only reads: per feasible
+        row, for every event e and slot t, d_scv (int32 [P, E, 45]: the change
+        of scv when e goes to t) and to_room (uint8 [P, E, 45]: the room it
+        would take, or MOVE1_CLASH / MOVE1_NO_ROOM), and summary (int32 [P, 6]:
+        scanned, feasible moves, improving ones, the least d_scv among them,
+        its event, its slot). All three are optional CUDA tensors. stream: a
+        torch.cuda.Stream (default: torch's current stream)."""
+        import torch
+        P = self._pop(slot, room)
+        cells = P * self.E * NUM_SLOTS
+        _opt_i32("summary", summary, 6 * P, "6 P", slot.device)
+        _opt_i32("d_scv", d_scv, cells, "P * E * 45", slot.device)
+        if to_room is not None and not (to_room.is_cuda and to_room.dtype == torch.uint8 and to_room.is_contiguous()
+                                        and to_room.numel() == cells and to_room.device == slot.device):
+            raise ValueError("to_room must be a contiguous uint8 CUDA tensor of P * E * 45 entries on the "
+                             "population's device")
+        _check(self.lib, self.lib.tt_move1_scan(self.handle, slot.data_ptr(), room.data_ptr(), P, _ptr(summary),
+                                                _ptr(d_scv), _ptr(to_room), self._stream(slot, stream)))
+
+    def move1_descent(self, slot, room, max_passes, scv=None, penalty=None, gain=None, passes=None, stream=None):
+        """tt_move1_descent in place on slot, room [P, E]: per feasible row, the
+        feasible single-event move of least d_scv is applied while it lowers
+        scv, at most max_passes times. scv, penalty (int32 [P], updated in
+        place), gain and passes (int32 [P]) are optional CUDA tensors."""
+        P = self._pop(slot, room)
+        for name, t in (("scv", scv), ("penalty", penalty), ("gain", gain), ("passes", passes)):
+            _opt_i32(name, t, P, "P", slot.device)
+        _check(self.lib, self.lib.tt_move1_descent(self.handle, slot.data_ptr(), room.data_ptr(), P, int(max_passes),
+                                                   _ptr(scv), _ptr(penalty), _ptr(gain), _ptr(passes),
+                                                   self._stream(slot, stream)))
 
     @staticmethod
     def _rng(rng, P):

@@ -46,6 +46,9 @@ FLAGS = (
          "guided: an event that clashes in both parents' slots goes to a slot of least cost"),
     Flag("--crossover", "crossover", "choice", ("uniform", "guided"), "--crossover must be uniform or guided",
          "the breeding operator: tt_ga_breed or tt_ga_breed_guided (Island(crossover=...))"),
+    Flag("--move1-descent", "move1_descent", "int", (0, INT_MAX), "--move1-descent must be a non-negative integer",
+         "max_passes of tt_move1_descent behind every search, timeslot swap and walk (Island(move1_descent=...)); "
+         "0: never called"),
 )
 KEYS = tuple(f.key for f in FLAGS)
 
@@ -74,7 +77,7 @@ def lahc_kempe_error(lahc, lahc_swap, lahc_kempe):
 
 
 def validate(init, kempe, kempe_max_chain, slot_swap, lahc, lahc_history, lahc_swap, crossover, crossover_repair,
-             lahc_kempe=0.0, lahc_kempe_max_chain=0, lahc_kempe_rooms="direct", lahc_walkers=1):
+             lahc_kempe=0.0, lahc_kempe_max_chain=0, lahc_kempe_rooms="direct", lahc_walkers=1, move1_descent=0):
     """Island's stage arguments: the first one out of range raises ValueError."""
     for ok, message in (
             (crossover in ("uniform", "guided"), "crossover must be 'uniform' or 'guided'"),
@@ -94,7 +97,8 @@ def validate(init, kempe, kempe_max_chain, slot_swap, lahc, lahc_history, lahc_s
             (lahc_kempe_rooms in ("direct", "augment"), "lahc_kempe_rooms must be 'direct' or 'augment'"),
             (lahc_kempe_rooms != "augment" or float(lahc_kempe) > 0, "lahc_kempe_rooms='augment' needs lahc_kempe > 0"),
             (1 <= int(lahc_walkers) <= 1024, "lahc_walkers must be from 1 to 1024"),
-            (int(lahc_walkers) == 1 or int(lahc) > 0, "lahc_walkers > 1 needs lahc > 0")):
+            (int(lahc_walkers) == 1 or int(lahc) > 0, "lahc_walkers > 1 needs lahc > 0"),
+            (int(move1_descent) >= 0, "move1_descent must be >= 0 (0: off)")):
         if not ok:
             raise ValueError(message)
 

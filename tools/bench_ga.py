@@ -228,6 +228,12 @@ def run_ga(a):
         stats = [i.lahc_walkers_stats() for i in isls]
         out["lahc"]["walkers"] = {"walkers": a.lahc_walkers, **{k: sum(s[k] for s in stats)
                                                                   for k in ("rows", "gain", "gainFirst", "winnerLater")}}
+    if a.move1_descent > 0:
+        stats = [i.move1_descent_stats() for i in isls]
+        k = {key: sum(s[key] for s in stats) for key in ("rows", "improved", "gain")}
+        moves = sum(s["meanPasses"] * s["improved"] for s in stats)
+        out["move1_descent"] = {"max_passes": a.move1_descent, **k,
+                                "mean_passes": moves / k["improved"] if k["improved"] else 0.0}
     if a.crossover == "guided":
         stats = [i.cx_stats() for i in isls]
         k = {key: sum(s[key] for s in stats) for key in ("children", "crossed", "clean", "cost", "repaired")}

@@ -113,7 +113,7 @@ def summarize(final, feas, trace, checkpoints):
 def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch", unique=False, stats_out=None,
                 init="random", kempe=0.0, kempe_max_chain=0, slot_swap=0, lahc=0, lahc_history=500,
                 lahc_swap=0.5, crossover="uniform", crossover_repair=False, lahc_kempe=0.0,
-                lahc_kempe_max_chain=0, lahc_kempe_rooms="direct", lahc_walkers=1):
+                lahc_kempe_max_chain=0, lahc_kempe_rooms="direct", lahc_walkers=1, move1_descent=0):
     import torch
 
     from ttga import native, stages
@@ -148,7 +148,7 @@ def device_runs(inst, seeds, pop, gens, steps, children=1, schedule="batch", uni
         feas[k] = 1 if isl.member_meta(0)[0] else 0
         final[k] = trace[k, -1]
         if stats_out is not None:
-            stage = next((s for s in ("cx", "lahc", "slot_swap", "kempe", "unique") if s in isl.on), None)
+            stage = next((s for s in ("move1_descent", "cx", "lahc", "slot_swap", "kempe", "unique") if s in isl.on), None)
             if stage:        # the first of these that is on
                 stats_out.append(getattr(isl, stage + "_stats")())
                 if stage == "lahc" and "lahc_kempe" in isl.on:
@@ -217,6 +217,8 @@ def main():
         "lahc_kempe": f"P > 0 (with --lahc N): compare Island(lahc=N, lahc_kempe=P) with Island(lahc=N)",
         "lahc_kempe_rooms": "augment (with --lahc N --lahc-kempe P): compare the room rules, same flags otherwise",
         "lahc_walkers": "K > 1 (with --lahc N): compare Island(lahc_walkers=K) with the single walk, same flags otherwise",
+        "move1_descent": "N > 0: compare Island(move1_descent=N) with the same flags without it "
+                         "(every other stage flag goes to both sides as given; no reference run)",
         "lahc_history": None, "lahc_swap": None, "crossover_repair": None, "lahc_kempe_max_chain": None})
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -243,6 +245,19 @@ def main():
         raise SystemExit("--crossover-repair needs --crossover guided")
     run = functools.partial(ab_compare, a, res, inst, seeds)
     rest = {"lahc": a.lahc, "lahc_history": a.lahc_history, "lahc_swap": a.lahc_swap, "slot_swap": a.slot_swap}
+    if a.move1_descent > 0:                          # every other stage flag goes to both arms as it was given
+        rest = {k: v for k, v in stages.island_kwargs(a).items() if k != "move1_descent"}
+        stages.validate(**{k: v for k, v in rest.items() if k != "unique"})      # what Island would refuse, before any run
+        res.update(rest, move1_descent=a.move1_descent)
+
+        def extras(st, with_stage):
+            if not with_stage:
+                return {}
+            improved = sum(s["improved"] for s in st)
+            return {"move1_descent_stats": st, "improved_share": improved / max(1, sum(s["rows"] for s in st)),
+                    "mean_passes": sum(s["meanPasses"] * s["improved"] for s in st) / improved if improved else 0.0}
+        return run(("device", "device_move1_descent"), (rest, dict(rest, move1_descent=a.move1_descent)),
+                   "move1_descent_vs_without", ("median_move1_descent", "median_without"), extras)
     if a.crossover == "guided":
         res["crossover"], res["crossover_repair"] = a.crossover, bool(a.crossover_repair)
         res.update(rest)
