@@ -117,6 +117,58 @@ __device__ __forceinline__ int mask_scv(uint64_t m) {
     return sc;
 }
 
+// The same terms, in fewer instructions, for a mask built as kShift5One << slot:
+// slot s at bit s + 5, so days 0-2 are the 9-bit fields at bits 5, 14, 23 of the low
+// word, days 3-4 those at bits 0, 9 of the high word, no day straddles the words, and a
+// slot byte of 63 (the sentinel column) shifts out. (Bits 0-4 of the low word and 18-31 of
+// the high word are clear in a valid row; an invalid row's outputs are the sentinels.)
+//  * single class, days 0-2 at once: g = the fields without their top slot, b = g + 255
+//    per field has the top bit set iff g != 0 and the low bits g - 1 (no carry leaves a
+//    field), t = g & b is g without its lowest slot, u = t + 255 has the top bit set iff g
+//    holds two or more. With h the field's own top slot, exactly one slot of nine is
+//    ~u & (b ^ h) at the top bit: 7 VALU with the popcount (gfx950's three-input
+//    v_bitop3_b32 takes t and the last two ANDs).
+//  * days 3-4: popcount of each field, then bit c of the constant 2 is [c == 1]: 7 VALU
+//    with the add.
+//  * >2 in a row: with gg = m less every field's top slot (g for the low word, one v_and
+//    for day 3; day 4's windows end in clear bits), gg & gg>>1 & m>>2 is m & m>>1 & m>>2
+//    without the windows that leave a day, so no kTripleMask: 7 VALU (two 64-bit shifts,
+//    one v_bitop3_b32 and one popcount per word).
+// 22 VALU in the built loop, with the sum, instead of mask_scv's 31 (10 for the windows,
+// 4 per day and one more for the day that straddles bit 32).
+constexpr uint64_t kShift5One = 32;
+constexpr uint32_t kShift5Low8 = (0xFFu << 5) | (0xFFu << 14) | (0xFFu << 23);      // fields' slots 0-7, low word
+constexpr uint32_t kShift5Top = (1u << 13) | (1u << 22) | (1u << 31);               // fields' slot 8, low word
+// bit c of k (c < 32): one v_bfe_u32
+__host__ __device__ inline uint32_t bit_of(uint32_t k, uint32_t c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_ubfe(k, c, 1u);
+#else
+    return (k >> c) & 1u;
+#endif
+}
+__host__ __device__ inline int mask_scv_shift5(uint64_t m) {
+    const uint32_t lo = (uint32_t)m, hi = (uint32_t)(m >> 32);
+    const uint32_t g = lo & kShift5Low8, b = g + kShift5Low8, t = g & b, u = t + kShift5Low8;
+    int sc = __builtin_popcount((b ^ lo) & ~u & kShift5Top);
+    const uint32_t c3 = (uint32_t)__builtin_popcount(hi & 0x1FFu), c4 = (uint32_t)__builtin_popcount((hi >> 9) & 0x1FFu);
+    sc += (int)(bit_of(2u, c3) + bit_of(2u, c4));
+    const uint32_t gh = hi & ~0x100u;
+    const uint64_t gg = ((uint64_t)gh << 32) | g;
+#if defined(__HIP_DEVICE_COMPILE__)
+    // pinned to one v_lshrrev_b64 per shift and one v_bitop3_b32 (AND of three) per word:
+    // left to itself the compiler shifts each word on its own and folds g's and gh's
+    // constants back in (9 VALU instead of 7)
+    uint64_t s1, s2;
+    asm("v_lshrrev_b64 %0, 1, %1" : "=&v"(s1) : "v"(gg));
+    asm("v_lshrrev_b64 %0, 2, %1" : "=&v"(s2) : "v"(m));
+    return sc + __builtin_popcount(__builtin_amdgcn_bitop3_b32(g, (uint32_t)s1, (uint32_t)s2, 0x80)) +
+           __builtin_popcount(__builtin_amdgcn_bitop3_b32(gh, (uint32_t)(s1 >> 32), (uint32_t)(s2 >> 32), 0x80));
+#else
+    return sc + __builtin_popcountll(gg & (gg >> 1) & (m >> 2));
+#endif
+}
+
 // Full-wave sum (every lane active): DPP row shifts + readlane, no LDS round
 // trips. Written out rather than __reduce_add_sync, whose library reduction
 // also carries a partial-EXEC path at every call site (code size: the local

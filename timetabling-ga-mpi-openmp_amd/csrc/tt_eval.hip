@@ -282,8 +282,14 @@ __device__ __forceinline__ uint32_t gap_slots4(uint32_t x) {
     return x + g9 + g18 + g36 + 3u * g27;
 }
 __device__ __forceinline__ uint8_t gap_slot(uint32_t s) { return (uint8_t)gap_slots4(s); }
-template <bool GAP>
-__device__ __forceinline__ int mask_terms(uint64_t m) { return GAP ? mask_scv_gap(m) : mask_scv(m); }
+// the three forms of a mask's terms: plain, gapped, and (SH5: eval_tile5's lane phase)
+// of a mask built from raw slots as kShift5One << slot (mask_scv_shift5, tt_common.h)
+template <bool GAP, bool SH5 = false>
+__device__ __forceinline__ int mask_terms(uint64_t m) {
+    static_assert(!(GAP && SH5), "one layout at a time");
+    if constexpr (SH5) return mask_scv_shift5(m);
+    return GAP ? mask_scv_gap(m) : mask_scv(m);
+}
 // K students of N ids whose dwords are r[0 .. K*N/2)
 template <int N, int K, bool GAP = false>
 __device__ __forceinline__ int students_scv(const uint8_t* my, const uint32_t* r) {
@@ -306,8 +312,9 @@ __device__ __forceinline__ int students_scv(const uint8_t* my, const uint32_t* r
 // A run of cnt students of N ids from dword p: one scalar load of K*N/2
 // dwords per step (K = 2 students when N <= 16), the next step's load issued
 // before this step's LDS reads (ping-pong registers, no copies).
-template <int N, int KMAX, bool GAP = false>
+template <int N, int KMAX, bool GAP = false, bool SH5 = false>
 __device__ __forceinline__ int run_scv(const uint8_t* my, const uint32_t* p, int cnt) {
+    static_assert(!SH5 || KMAX == 1, "the shifted mask is built by the one-student step only");
     constexpr int K = N <= 16 ? KMAX : 1;
     constexpr int ST = K * N / 2;
     const int steps = cnt / K;
@@ -329,8 +336,8 @@ __device__ __forceinline__ int run_scv(const uint8_t* my, const uint32_t* p, int
             for (int j = 0; j < N; ++j) sl[j] = my[(cur[j >> 1] >> (16 * (j & 1))) & 0xFFFFu];
             uint64_t m = 0;
 #pragma unroll
-            for (int j = 0; j < N; ++j) m |= 1ull << (sl[j] & 63);
-            sc += mask_terms<GAP>(m);
+            for (int j = 0; j < N; ++j) m |= (SH5 ? kShift5One : 1ull) << (sl[j] & 63);
+            sc += mask_terms<GAP, SH5>(m);
 #pragma unroll
             for (int j = 0; j < N / 2; ++j) cur[j] = nxt[j];
         }
@@ -375,7 +382,7 @@ __device__ __noinline__ int run_scv_any(const uint8_t* my, const ConstU32* p, in
     }
     return sc;
 }
-template <int KMAX, bool GAP = false>
+template <int KMAX, bool GAP = false, bool SH5 = false>
 __device__ __forceinline__ int lane_scv_runs(const uint8_t* my, const DevProblem& pb, int r0, int r1) {
     const ConstI32* runs = (const ConstI32*)pb.srun;
     int sc = 0;
@@ -383,7 +390,7 @@ __device__ __forceinline__ int lane_scv_runs(const uint8_t* my, const DevProblem
         const int n = runs[4 * k], off = runs[4 * k + 1], cnt = runs[4 * k + 2];
         const uint32_t* p = pb.sid + off;
         switch (n) {
-#define TT_RUN(N) case N: sc += run_scv<N, KMAX, GAP>(my, p, cnt); break;
+#define TT_RUN(N) case N: sc += run_scv<N, KMAX, GAP, SH5>(my, p, cnt); break;
             TT_RUN(2) TT_RUN(4) TT_RUN(6) TT_RUN(8) TT_RUN(10) TT_RUN(12) TT_RUN(14) TT_RUN(16)
             TT_RUN(18) TT_RUN(20) TT_RUN(22) TT_RUN(24) TT_RUN(26) TT_RUN(28) TT_RUN(30) TT_RUN(32)
 #undef TT_RUN
@@ -699,7 +706,7 @@ __global__ __launch_bounds__(64 * NW, 4) void eval_tile5_kernel(DevProblem pb, c
         uint32_t lsp;
         asm volatile("v_mul_u32_u24 %0, %1, %2" : "=v"(lsp) : "v"(lane), "s"(SP));
         __builtin_amdgcn_s_setprio(kT5PrioLane);
-        const int sc = (!(ablate & 1) && r0 < r1) ? lane_scv_runs<1>(tile + lsp, pb, r0, r1) : 0;
+        const int sc = (!(ablate & 1) && r0 < r1) ? lane_scv_runs<1, false, true>(tile + lsp, pb, r0, r1) : 0;
         part[wv * 64 + lane] = sc;
 
         // ---- wave phase (wave = individual): hcv terms + last-slot term

@@ -8,7 +8,7 @@ REV=$1; NAME=$2
 SRC=$(mktemp -d /tmp/ab_XXXX)
 mkdir -p "$SRC/x/csrc" "$SRC/include" "$REPO/ab_libs"
 if [ "$REV" = wt ]; then
-  cp "$REPO"/timetabling-ga-mpi-openmp_amd/csrc/* "$SRC/x/csrc/"; cp "$REPO"/include/*.h "$SRC/include/"
+  cp "$REPO"/timetabling-ga-mpi-openmp_amd/csrc/* "$SRC/x/csrc/"; cp -r "$REPO"/include/. "$SRC/include/"
 else
   git -C "$REPO" archive "$REV" timetabling-ga-mpi-openmp_amd/csrc include | tar -x -C "$SRC"
   mv "$SRC"/timetabling-ga-mpi-openmp_amd/csrc/* "$SRC/x/csrc/"
